@@ -6,9 +6,23 @@
         bench.py --gpus N --steps K --warmup W
 
 One step = model forward + CtdetLoss + backward + gradient all-reduce (N>1) + Adam, on a synthetic batch that
-is already resident in HBM.  Rank 0 prints ONE JSON line (contract in the task description) that also carries
+is already resident in HBM.  Adam runs with lr 0: every step does the whole update's work, but the weights stay at their seeded
+values, so every step computes the same function of the same inputs.  (With lr > 0 the float-atomic reductions of a few backward
+kernels differ in the last bits from run to run, and Adam's sign-like first updates amplify that to per-mille differences of the
+loss within a few steps: outputs of two runs could not be compared.)  Rank 0 prints ONE JSON line: metric, value (images/s over the timed steps), unit,
+higher_is_better, dtype, ms_per_step (wall time of one timed step) and the configuration.  A plain run does only that:
+set-up, warm-up, the timed steps, --dump-outputs if given, the line.
+
+    --dump-outputs DIR   after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32):
+                         loss, and the parameters, their gradients and the float buffers (BatchNorm statistics) after
+                         it -- each concatenated in state_dict order, a fixed seeded sample where longer than 3 Mi
+                         elements (--config rgb-encoder: its three outputs and the gradients).  The inputs are seeded: same arguments, same inputs, so two builds compare output
+                         for output.
+    --full               everything else the benchmark measures, after the timed steps (each has a --no-* switch):
   roofline     : fp32-MFMA roofline of the dominant kernel family (the implicit-GEMM kernels), measured live
-                 with events on the launch stream in an extra instrumented step after the timed region;
+                 with events on the launch stream in an extra instrumented step; roofline_hbm beside it;
+  arithmetic.native_fp32_mfma_step, config.collective_path, mpjpe, bf16_per_gpu (the bf16 B=32 / B=64 legs),
+  check_grads (N > 1);
   cpu_baseline : the CPU oracle (oracle/pdfnet_cpu.py) timed on this box's host cores on a bounded sample.
 """
 import argparse
@@ -360,6 +374,32 @@ def _flush_c_stdout():
         pass
 
 
+DUMP_MAX_ELEMS = 3 << 20                               # per array (12.6 MB of float32): four arrays at most, 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} -> path/<name>.npy, float32 (float64 tensors stay float64).  An array of more than DUMP_MAX_ELEMS
+    elements is flattened and replaced by a fixed sample: sorted indices drawn from a seeded generator, the same on every run and build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(20240917)
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(path, name + '.npy'), t.numpy())
+
+
+def flat_state(model):
+    """The arrays a caller of the train step holds after it: parameters, their gradients, float buffers -- each concatenated in state_dict order."""
+    params = [p for _, p in model.named_parameters()]
+    bufs = [b for _, b in model.named_buffers() if b.is_floating_point()]
+    cat = lambda ts: torch.cat([t.detach().reshape(-1).float() for t in ts]) if ts else torch.zeros(0)   # noqa: E731
+    return {"params": cat(params), "grads": cat([p.grad if p.grad is not None else torch.zeros_like(p) for p in params]), "buffers": cat(bufs)}
+
+
 def pmc_traffic():
     """-> ({kernel symbol: HBM bytes per launch}, bytes per launch of the whole GEMM family, source tag).  PMC counters cannot be read
     from inside this process: the figures come from the last committed profile (tools/profile_step.sh -> profiles/*_pmc_traffic.json,
@@ -544,14 +584,18 @@ def rgb_encoder_bench(args, dev, rank, world):
         x0, emb0, x1 = enc.rgb_encoder(img)
         (x0.pow(2).mean() + emb0.pow(2).mean() + x1.pow(2).mean()).backward()
         F.join_wgrad()
+        return x0, emb0, x1
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     t0 = time.time()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     dt = time.time() - t0
+    if args.dump_outputs:
+        grads = torch.cat([p.grad.detach().reshape(-1) if p.grad is not None else torch.zeros_like(p).reshape(-1) for p in params])
+        dump_outputs(args.dump_outputs, {"x0": last[0], "emb0": last[1], "x1": last[2], "grads": grads})
     # algorithmic FLOPs of this sub-path, SURVEY 8(d): a1 10.68 + a2 15.57 + a3 19.33 + a7 0.01 GF/img forward, x3 for the step
     gf_img = 3 * (10.68 + 15.57 + 19.33 + 0.01) * (R / 256.0) ** 2
     out = {"metric": "RGB-only encoder fwd+bwd images/sec @%dx%d B=%d" % (R, R, B), "value": round(B * args.steps / dt, 2), "unit": "images/s",
@@ -764,14 +808,19 @@ def main():
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-mpjpe', action='store_true')
     ap.add_argument('--broadcast-buffers', action='store_true', help="DDP's per-iteration BN-buffer broadcast (base_trainer.py:94-95)")
-    ap.add_argument('--check-grads', action='store_true', help='(default for --gpus > 1) verify the reduced gradient against an all_gather of the rank-local ones')
+    ap.add_argument('--check-grads', action='store_true', help='(default for --gpus > 1 with --full) verify the reduced gradient against an all_gather of the rank-local ones')
     ap.add_argument('--no-check-grads', action='store_true')
     ap.add_argument('--no-collective-path', action='store_true', help='skip the one-rank RCCL measurement of the reduction path (config.collective_path_ms)')
     ap.add_argument('--no-native-leg', action='store_true', help='skip the all-native-fp32-MFMA steps timed beside the shipped (x3) step (arithmetic.native_fp32_mfma_step)')
     ap.add_argument('--no-bf16-legs', action='store_true', help='skip the bf16 B=32 / B=64 per-GPU legs (bf16_per_gpu) of the default fp32 run')
-    ap.add_argument('--gemm-shapes', default=None, help='write the per-shape table of the instrumented step to this file')
-    ap.add_argument('--hbm-shapes', default=None, help='the same for the HBM-bound entry points (integer arguments, algorithmic MB, ms, GB/s)')
+    ap.add_argument('--gemm-shapes', default=None, help='(--full) write the per-shape table of the instrumented step to this file')
+    ap.add_argument('--hbm-shapes', default=None, help='(--full) the same for the HBM-bound entry points (integer arguments, algorithmic MB, ms, GB/s)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also measure and check everything else: roofline, native-fp32 step, '
+                    'collective path, MPJPE, bf16 legs, check_grads (N > 1), CPU baseline (each can be left out with its --no-* switch)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float32)')
     args = ap.parse_args()
+    if (args.gemm_shapes or args.hbm_shapes) and not args.full:
+        ap.error('--gemm-shapes / --hbm-shapes come from the instrumented step of --full')
     if args.batch is None:
         args.batch = 8 if args.config == 'rgb-encoder' else 32
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -808,7 +857,7 @@ def main():
     loss = CtdetLoss(opt, consts).to(dev)
     if args.graph and os.environ.get('PDF_GRAPH_WGRAD_STREAM') == '0':
         F.ASYNC_WGRAD = False              # (the weight-gradient branch inside the capture: grouped launches, Trainer.GRAPH_WGRAD_GROUP -- r05_wgrad_group.txt)
-    trainer = Trainer(opt, model, loss, lr=1e-4, use_graph=args.graph, broadcast_buffers=args.broadcast_buffers,
+    trainer = Trainer(opt, model, loss, lr=0.0, use_graph=args.graph, broadcast_buffers=args.broadcast_buffers,
                       grad_comm_dtype=torch.bfloat16 if bf16 else None)   # world > 1: replicas synced from rank 0
     batch = to_device(synthetic_train_batch(B, R, seed=1 + rank, consts=consts), dev)
     rccl_ranks = 1
@@ -841,6 +890,8 @@ def main():
         dt = float(t)
     loss_val = float(last)
     assert loss_val == loss_val, "loss is NaN"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(loss=last, **flat_state(model)))
 
     out = {
         "metric": "train-step images/sec @256x256 RGB-D B=32", "value": round(world * B * args.steps / dt, 2),
@@ -852,7 +903,7 @@ def main():
                                "%s, %dx%d" % ("3/4" if bf16 else "2", B, "bf16 MFMA GEMMs (fp32 accumulate, fp32 master weights / statistics / loss)" if bf16 else "fp32", R, R), "global_batch": world * B, "parallelism": "dp%d" % world,
                    "launch": "hipGraph(fwd+loss+bwd) + fused Adam" if args.graph else "eager, weight-gradient kernels overlapped on a side HIP stream, fused Adam", "final_loss": round(loss_val, 4),
                    "rccl_ranks": rccl_ranks, "allreduce_mb_per_step": round(trainer.n_live * (2 if bf16 else 4) / 1e6, 1) if world > 1 else 0.0,
-                   "broadcast_buffers": bool(args.broadcast_buffers),
+                   "broadcast_buffers": bool(args.broadcast_buffers), "adam_lr": 0.0,
                    # what pdfnet_amd/taped.py keeps alive for the life of the process (the trunk's activations of every recorded signature)
                    "taped_pinned_mb": round(getattr(model.encoder.__dict__.get('_trunk_seg'), 'pinned_bytes', lambda: 0)() / 1e6, 1)},
     }
@@ -869,7 +920,7 @@ def main():
                 (["the linear products of the fused mesh decoder (GCN blocks, attention projections and MLPs, forward and data gradients; operands split in registers)"] if x3_mode & 4 else [])),
             "everything_else": "native fp32 MFMA (v_mfma_f32_32x32x2_f32)",
             "error_vs_float64": "x3 products 0.31-0.37x the native kernel's rms error, max error 0.35-0.45x (profiles/r06_x3_bench.txt; enforced by tests/test_x3_gpu.py)"}
-        if world == 1 and not args.graph and not args.no_native_leg:
+        if args.full and world == 1 and not args.graph and not args.no_native_leg:
             try:
                 F.set_x3(0)
                 kn = max(5, args.steps // 3)
@@ -889,7 +940,7 @@ def main():
                 for _ in range(2):
                     trainer.train_step(batch)                  # (the instrumented step below runs the shipped configuration, allocator warm)
                 barrier()
-    if world == 1 and not bf16 and not args.graph and not args.no_collective_path:
+    if args.full and world == 1 and not bf16 and not args.graph and not args.no_collective_path:
         try:
             cp = collective_path(trainer, batch)
             out["config"]["collective_path_ms"] = cp["collective_path_ms"]
@@ -897,11 +948,11 @@ def main():
         except Exception as e:                                 # noqa: BLE001 -- the headline line must still be printed
             out["config"]["collective_path"] = {"error": "%s: %s" % (type(e).__name__, e)}
     mp_batch = None
-    if not args.no_mpjpe:
+    if args.full and not args.no_mpjpe:
         out["mpjpe"], mp_batch = mpjpe_report(trainer, consts, R, min(B, 8), dev)      # every rank takes part (all-reduced sums)
-    if world > 1 and not args.no_check_grads:
+    if world > 1 and (args.check_grads or (args.full and not args.no_check_grads)):
         out["check_grads"] = check_grads(trainer, batch, world, dev)
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # instrumented eager step: events around every implicit-GEMM entry point on the launch stream
         trainer.use_graph = False
         trainer.collectives = False        # rank-local step: the other ranks are already past their last collective
@@ -990,9 +1041,9 @@ def main():
             "fps_single_wave": fps_hbm(dev, Bc=64, N=1024, S=512),   # the reference's SAMPLE_NUM / sample_num_level1 (opts.py:226-228): one wave per cloud
         }
         F.USE_SIDE_STREAMS = True
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     parity_half = mpjpe_parity_hip_half(trainer, dev, mp_batch) if (want_cpu and mp_batch is not None) else None
-    if rank == 0 and world == 1 and not bf16 and not args.no_bf16_legs and args.batch == 32:
+    if args.full and rank == 0 and world == 1 and not bf16 and not args.no_bf16_legs and args.batch == 32:
         # BASELINE configs[3] / [4] per GPU, driver-timed in the same run: short legs after the fp32 headline.
         # The fp32 model, trainer and batches go first (measured: with them alive the legs ran 8-13 ms per step slower than the
         # same step in a fresh process -- twice the tracked Python objects for the collector, twice the live allocations)

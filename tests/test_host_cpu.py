@@ -245,6 +245,31 @@ def test_bench_gpus_n_launches_its_own_ranks_as_a_child_process():
     assert r.returncode != 0 and 'WORLD_SIZE=1' in r.stderr
 
 
+def test_bench_dump_outputs_are_float_bounded_and_seeded(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 (float64 stays float64) .npy files; an array longer than DUMP_MAX_ELEMS becomes the same
+    seeded sample on every call, so two builds compare element for element; flat_state lists parameters, gradients and float buffers."""
+    import numpy as np
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 5, dtype=torch.float32)
+    small = torch.randn(3, 4, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"big": big, "small": small, "ints": torch.arange(4)})
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big.clone()})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) >= 0) and a[0] >= 0 and a[-1] <= big[-1].item()
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy())
+    assert np.load(tmp_path / "a" / "ints.npy").dtype == np.float32
+    assert 4 * 4 * bench.DUMP_MAX_ELEMS <= 64e6                 # at most four arrays per dump
+    m = torch.nn.Sequential(torch.nn.Linear(3, 2), torch.nn.BatchNorm1d(2), torch.nn.Linear(2, 1))
+    m(torch.randn(4, 3))[:, 0].sum().backward()
+    m[2].weight.grad = None
+    st = bench.flat_state(m)
+    n = sum(p.numel() for p in m.parameters())
+    assert st["params"].shape == (n,) and st["grads"].shape == (n,) and st["buffers"].shape == (4,)
+    assert torch.equal(st["grads"][:6], m[0].weight.grad.reshape(-1)) and float(st["grads"][-3:-1].abs().sum()) == 0.0
+
+
 def test_rejected_call_leaves_no_armed_slot():
     """the pdf_set_* hand-overs are compat wrappers over the explicit PdfCallOpts of the `_x` entry points; a plain
     entry point takes AND CLEARS every slot before it looks at an argument, so a call that is rejected (PDF_E_BADARG) or returns early
