@@ -178,6 +178,29 @@ int pdf_bn_relu_maxk_fwd(const float* y, int ldy, int C, long R, int K, const fl
 int pdf_bn_relu_maxk_bwd(const float* dout, int lddo, const int* arg, const float* y, int ldy, const float* save_mean, const float* save_rstd,
                          const float* gamma, const float* scale, const float* shift, int C, long R, int K,
                          float* dy, int lddy, float* dgamma, float* dbeta, int accumulate, float* ws, void* stream);
+/* A whole set-abstraction MLP after its first 1x1 convolution, fused with recomputation (intaghand_encoder.py:48-65,67-85;
+ * csrc/safused.hip): y1 = u[b, idx[b,s,k], :] - v[b,s,:] (the gather_sub identity), then three times BatchNorm -> ReLU with the
+ * 1x1 convolutions w2 [C2][C1] and w3 [C3][C2] between them, then the max over the K neighbours: out [Bc*S][C3].  No [rows][C]
+ * activation is written: every pass rebuilds the K rows of a centroid in LDS from u [Bc][N][C1], v [Bc][S][C1] and idx int32 [Bc][S][K].
+ * training: batch statistics over the Bc*S*K rows, running statistics updated (momentum, unbiased variance); arg int32 / zsel
+ * [Bc*S][C3] (the selected k and pre-activation) and saved [4*(C1+C2+C3)] feed the backward.
+ * Else the running statistics are used (arg / zsel may be NULL).  The backward writes dz1 [Bc*S*K][C1], the gradient of y1 (a
+ * transient buffer for pdf_gather_sub_bwd_sorted), and the gradients of w2, b2, w3, b3 and the three (gamma, beta) pairs (written,
+ * not accumulated).  Deterministic (no float atomics).  K % 16 == 0, 16 <= K <= 64; C1, C2, C3 multiples of 16 up to 256;
+ * C2*C1 and C3*C2 <= 32768; 4*K*(C1 + C2 + C3 + 12) <= 159 KiB (the backward's LDS); other shapes: PDF_E_BADARG.  The saved
+ * statistics hold per layer mean, rstd, scale = gamma*rstd and beta; BatchNorm is applied as relu(scale*(z - mean) + beta).  ws: pdf_sa_fused_workspace_floats(Bc, S, K, C1, C2, C3) floats (forward and backward). */
+long pdf_sa_fused_workspace_floats(int Bc, int S, int K, int C1, int C2, int C3);
+int pdf_sa_fused_fwd(const float* u, const float* v, const int* idx, int Bc, int N, int S, int K, int C1, int C2, int C3,
+                     const float* w2, const float* b2, const float* w3, const float* b3,
+                     const float* gamma1, const float* beta1, const float* gamma2, const float* beta2, const float* gamma3, const float* beta3,
+                     float* rmean1, float* rvar1, float* rmean2, float* rvar2, float* rmean3, float* rvar3, float momentum, float eps, int training,
+                     float* out, int* arg, float* zsel, float* saved, float* ws, long ws_floats, void* stream);
+int pdf_sa_fused_bwd(const float* dout, const float* u, const float* v, const int* idx, int Bc, int N, int S, int K, int C1, int C2, int C3,
+                     const float* w2, const float* b2, const float* w3, const float* b3,
+                     const float* out, const int* arg, const float* zsel, const float* saved,
+                     float* dz1, float* dw2, float* db2, float* dw3, float* db3,
+                     float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, float* dgamma3, float* dbeta3,
+                     float* ws, long ws_floats, void* stream);
 
 /* ---- normalisation (csrc/norm.hip) ------------------------------------------------------------ */
 

@@ -1804,6 +1804,95 @@ def bn_relu_max_over_k(x, gamma, beta, rmean, rvar, K, training, momentum=0.1, e
     return _BnReluMaxK.apply(x, gamma, beta, rmean, rvar, K, training, momentum, eps)
 
 
+# ---- fused set-abstraction MLP with recomputation (csrc/safused.hip): opt-in, fp32 mode only (the encoder keeps the unfused path in bf16 mode)
+SA_FUSED = _os.environ.get("PDFNET_SA_FUSED", "0") != "0"
+
+
+def set_sa_fused(on):
+    """PointNet++ set-abstraction levels 1 and 2 through sa_mlp_fused (True) or the per-layer kernels (False, the default)."""
+    global SA_FUSED
+    SA_FUSED = bool(on)
+
+
+_sa_ws_cache = {}
+
+
+def _sa_ws(shape, dev):
+    n = _sa_ws_cache.get(shape)
+    if n is None:
+        n = _sa_ws_cache[shape] = _L().pdf_sa_fused_workspace_floats(*shape)
+    return _ws(n, dev), n
+
+
+class _SaMlpFused(Function):
+    """out [Bc*S, C3] = max_k relu(BN3(W3 relu(BN2(W2 relu(BN1(y1)) + b2)) + b3)), y1[b,s,k] = u[b, idx[b,s,k]] - v[b,s].
+    Only O(points) tensors are kept for the backward (u, v, idx, the weights, out / arg / zsel [Bc*S, C3], the statistics); the
+    backward rebuilds the rows three times and hands the gradient of y1 -- the one rows-sized tensor, freed at once -- to the
+    deterministic gather_sub backward."""
+
+    @staticmethod
+    def forward(ctx, u, v, idx, w2, b2, w3, b3, g1, g2, g3, be1, be2, be3, rm1, rv1, rm2, rv2, rm3, rv3, training, momentum, eps):
+        hip.require_gpu(u, v, idx, w2, w3)
+        u, v, idx, w2, w3 = u.contiguous(), v.contiguous(), idx.contiguous(), w2.contiguous(), w3.contiguous()
+        Bc, N, C1 = u.shape
+        S, K = idx.shape[1], idx.shape[2]
+        C2, C3 = w2.shape[0], w3.shape[0]
+        if v.shape != (Bc, S, C1) or w2.shape[1] != C1 or w3.shape[1] != C2:
+            raise ValueError("pdfnet_amd: sa_mlp_fused wants u [Bc,N,C1], v [Bc,S,C1], idx [Bc,S,K], w2 [C2,C1], w3 [C3,C2]")
+        dev = u.device
+        out = torch.empty((Bc * S, C3), device=dev)
+        saved = torch.empty(4 * (C1 + C2 + C3), device=dev)
+        arg = torch.empty((Bc * S, C3), dtype=torch.int32, device=dev) if training else None
+        zsel = torch.empty((Bc * S, C3), device=dev) if training else None
+        shape = (Bc, S, K, C1, C2, C3)
+        ws, n = _sa_ws(shape, dev)
+        _L().pdf_sa_fused_fwd(ptr(u), ptr(v), ptr(idx), Bc, N, S, K, C1, C2, C3, ptr(w2), ptr(b2), ptr(w3), ptr(b3),
+                              ptr(g1), ptr(be1), ptr(g2), ptr(be2), ptr(g3), ptr(be3), ptr(rm1), ptr(rv1), ptr(rm2), ptr(rv2), ptr(rm3), ptr(rv3),
+                              float(momentum), float(eps), int(training), ptr(out), ptr(arg), ptr(zsel), ptr(saved), ptr(ws), n, stream())
+        ctx.save_for_backward(u, v, idx, w2, b2, w3, b3, out, arg, zsel, saved)
+        ctx.cfg = (Bc, N, S, K, C1, C2, C3, training)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        u, v, idx, w2, b2, w3, b3, out, arg, zsel, saved = ctx.saved_tensors
+        Bc, N, S, K, C1, C2, C3, training = ctx.cfg
+        if not training:
+            raise RuntimeError("pdfnet_amd: BatchNorm backward in eval mode is not implemented")
+        if (2 * N + 1) * 4 > 160 * 1024:
+            raise RuntimeError("pdfnet_amd: sa_mlp_fused backward needs N <= 20479 points (deterministic gather backward)")
+        dev = dout.device
+        g = dout.contiguous()
+        dw2, dw3 = torch.empty_like(w2), torch.empty_like(w3)
+        db2, db3 = torch.empty(C2, device=dev), torch.empty(C3, device=dev)
+        dg = [torch.empty(c, device=dev) for c in (C1, C2, C3)]
+        dbe = [torch.empty(c, device=dev) for c in (C1, C2, C3)]
+        L = _L()
+        ws, n = _sa_ws((Bc, S, K, C1, C2, C3), dev)
+        dz1 = torch.empty((Bc, S, K, C1), device=dev)          # the gradient of y1: transient
+        L.pdf_sa_fused_bwd(ptr(g), ptr(u), ptr(v), ptr(idx), Bc, N, S, K, C1, C2, C3, ptr(w2), ptr(b2), ptr(w3), ptr(b3),
+                           ptr(out), ptr(arg), ptr(zsel), ptr(saved), ptr(dz1), ptr(dw2), ptr(db2), ptr(dw3), ptr(db3),
+                           ptr(dg[0]), ptr(dbe[0]), ptr(dg[1]), ptr(dbe[1]), ptr(dg[2]), ptr(dbe[2]), ptr(ws), n, stream())
+        start = torch.empty((Bc, N + 1), dtype=torch.int32, device=dev)
+        lst = torch.empty((Bc, S * K), dtype=torch.int32, device=dev)
+        L.pdf_invert_index(ptr(idx), Bc, N, S * K, ptr(start), ptr(lst), None, stream())
+        du = torch.empty((Bc, N, C1), device=dev)
+        dv = torch.empty((Bc, S, C1), device=dev)
+        L.pdf_gather_sub_bwd_sorted(ptr(dz1), C1, ptr(start), ptr(lst), ptr(du), C1, ptr(dv), C1, Bc, N, S, K, C1, stream())
+        del dz1
+        return (du, dv, None, dw2, db2, dw3, db3, dg[0], dg[1], dg[2], dbe[0], dbe[1], dbe[2]) + (None,) * 9
+
+
+def sa_mlp_fused(u, v, idx, w2, b2, w3, b3, gamma1, gamma2, gamma3, beta1, beta2, beta3, rmean1, rvar1, rmean2, rvar2, rmean3, rvar3,
+                 training, momentum=0.1, eps=1e-5):
+    """A set-abstraction MLP after its first 1x1 convolution, fused with recomputation: u = conv1(points) [Bc,N,C1] (bias included),
+    v = conv1 without bias of the centres [Bc,S,C1], idx int32 [Bc,S,K] -> out [Bc*S, C3].  Same values as
+    gather_sub -> batch_norm(relu) -> linear -> batch_norm(relu) -> linear -> bn_relu_max_over_k (training: batch statistics and the
+    running-statistics update; else the running statistics).  Ties over k: the first k whose pre-activation z3 is extreme."""
+    return _SaMlpFused.apply(u, v, idx, w2, b2, w3, b3, gamma1, gamma2, gamma3, beta1, beta2, beta3, rmean1, rvar1, rmean2, rvar2,
+                             rmean3, rvar3, bool(training), momentum, eps)
+
+
 # ----------------------------------------------------------------------------------------------
 class _Cheby2(Function):
     """x [B,V,F] -> [B,V,2F] = interleave(x, L x); ell = (col, val, colT, valT, width)."""

@@ -151,6 +151,30 @@ class PointNet_Plus(nn.Module):
         return seq[7].relu_max_over_k(seq[6](x, stats=seq[7].training), K)
 
     @staticmethod
+    def _sa_fused_on(seq):
+        """F.SA_FUSED (PDFNET_SA_FUSED / F.set_sa_fused): levels 1 and 2 run as ONE fused MLP with recomputation (F.sa_mlp_fused) --
+        fp32 mode only: under the bf16 GEMM precision the per-layer path below is kept.  PDFNET_LAZY_SA_BN does not apply to it."""
+        bns = (seq[1], seq[4], seq[7])
+        return F.SA_FUSED and not F._GEMM_BF16 and bns[0].training == bns[1].training == bns[2].training
+
+    @staticmethod
+    def _sa_fused(seq, rows, S, K, r2):
+        """The whole MLP of a level (:48-65 / :67-85) on the fused kernels: first 1x1 convolution per POINT (as in _group_conv), then
+        F.sa_mlp_fused -- no [rows, C] activation is kept between forward and backward.  -> [B*S, C3]."""
+        idx = F.knn_ball_indices(rows, S, K, r2)
+        conv = seq[0]
+        w = conv.matrix(rows.shape[-1])
+        u = F.linear(rows, w, conv.bias, fp32=True)
+        ctr = torch.nn.functional.pad(rows[:, :S, :3], (0, rows.shape[-1] - 3))
+        v = F.linear(ctr, w, fp32=True)
+        bns = (seq[1], seq[4], seq[7])
+        for bn in bns:
+            bn.track_call()
+        return F.sa_mlp_fused(u, v, idx, seq[3].weight.flatten(1), seq[3].bias, seq[6].weight.flatten(1), seq[6].bias,
+                              *[bn.weight for bn in bns], *[bn.bias for bn in bns],
+                              *[t for bn in bns for t in (bn.running_mean, bn.running_var)], bns[0].training, bns[0].momentum, bns[0].eps)
+
+    @staticmethod
     def _group_conv(conv, rows, S, K, r2):
         """group_points / group_points_2 (lib/utils/utils.py:134-188) followed by the MLP's first 1x1 convolution, without the
         grouped tensor: the convolution is linear, so it is applied once per POINT and its rows are gathered --
@@ -179,15 +203,22 @@ class PointNet_Plus(nn.Module):
         if chain:
             e0, emb0 = e0
         pts = self.sft0(cloud, e0)                                                         # [B,1024,3]   (:120-122)
-        y1 = self._group_conv(self.netR_1[0], F.pad2d(pts.reshape(-1, 3), pts.shape[0] * pts.shape[1], _pad16(3)).view(pts.shape[0], pts.shape[1], _pad16(3)), S1, K, o.ball_radius)   # (:123,:49)
-        x = self._mlp_max(self.netR_1, y1, K)                                               # [B*S1,128]   (:132)
+        rows1 = F.pad2d(pts.reshape(-1, 3), pts.shape[0] * pts.shape[1], _pad16(3)).view(pts.shape[0], pts.shape[1], _pad16(3))
+        if self._sa_fused_on(self.netR_1):
+            x = self._sa_fused(self.netR_1, rows1, S1, K, o.ball_radius)                    # [B*S1,128]
+        else:
+            y1 = self._group_conv(self.netR_1[0], rows1, S1, K, o.ball_radius)             # (:123,:49)
+            x = self._mlp_max(self.netR_1, y1, K)                                           # [B*S1,128]   (:132)
         e1 = F.gather_rows(emb1, choose[:, :S1], R, 1, chain=chain)                        # [B,S1,64]    (:125-127)
         if chain:
             e1, emb1 = e1
         x = torch.cat((pts[:, :S1], x.view(B, S1, 128), x.new_zeros(B, S1, _pad16(131) - 131)), 2)   # [B,S1,131 | 0]   (:134)
         x = self.sft1(x, e1)                                                               #              (:137)
-        y1 = self._group_conv(self.netR_2[0], x, S2, K, o.ball_radius2)                    # (:139,:68)
-        y = self._mlp_max(self.netR_2, y1, K)                                               # [B*S2,256]
+        if self._sa_fused_on(self.netR_2):
+            y = self._sa_fused(self.netR_2, x, S2, K, o.ball_radius2)                        # [B*S2,256]
+        else:
+            y1 = self._group_conv(self.netR_2[0], x, S2, K, o.ball_radius2)                # (:139,:68)
+            y = self._mlp_max(self.netR_2, y1, K)                                           # [B*S2,256]
         return (x, y, emb0, emb1) if chain else (x, y)
 
     def stage_b(self, x, y, emb2, choose, chain=False):

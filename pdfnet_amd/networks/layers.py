@@ -119,21 +119,21 @@ class BatchNorm(nn.Module):
         BatchNorm.flush_counters()
         super()._save_to_state_dict(destination, prefix, keep_vars)
 
-    def forward(self, x, relu=False, res=None, lazy=False):
+    def track_call(self):
+        """Count one training-mode call for num_batches_tracked (applied by flush_counters)."""
         if self.training:
             if self._pending == 0:
                 BatchNorm._dirty.append(self)
             self._pending += 1
+
+    def forward(self, x, relu=False, res=None, lazy=False):
+        self.track_call()
         return F.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var,
                             self.training, self.momentum, self.eps, relu, res, lazy)
 
-
     def relu_max_over_k(self, x, K):
         """relu(self(x)) followed by the max over groups of K consecutive rows, fused (F.bn_relu_max_over_k)."""
-        if self.training:
-            if self._pending == 0:
-                BatchNorm._dirty.append(self)
-            self._pending += 1
+        self.track_call()
         return F.bn_relu_max_over_k(x, self.weight, self.bias, self.running_mean, self.running_var, K, self.training, self.momentum, self.eps)
 
 
