@@ -37,8 +37,6 @@ int pdf_linear_fwd(const float* x, const float* w, const float* bias, float* y,
 int pdf_linear_bwd_weight(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
                           int M, int N, int K, int ldx, int lddy, int accumulate, void* stream);
 long pdf_wgrad_workspace_floats(int M, int NI, int NJ);
-/* measurement aids (bench.py): BM*1000+BN of the calling thread's last implicit-GEMM launch (0 = streaming small-K
- * kernel), and the number of implicit-GEMM kernels it has launched so far (one entry point may launch several) */
 /* Allocates the library's ticket-counter ring (csrc/common.h pdf_last_block_arrives: in-launch finalisation of BatchNorm
  * statistics and weight-gradient slabs).  Called once per process after the device is selected, outside any stream capture;
  * the entry points call it lazily otherwise. */
@@ -72,6 +70,8 @@ int pdf_stream_wait(void* waiter, void* signaler);
  * weights and fp32 normalisation / loss statistics).  Process-wide; set before the first step. */
 int pdf_set_gemm_precision(int bf16);
 int pdf_debug_gemm_precision(void);
+/* measurement aids (bench.py): BM*1000+BN of the calling thread's last implicit-GEMM launch (0 = streaming small-K
+ * kernel), and the number of implicit-GEMM kernels it has launched so far (one entry point may launch several) */
 int pdf_debug_last_tile(void);
 int pdf_debug_igemm_launches(void);
 /* dx[M][K] = dy[M][N] w[N][K] (autograd of nn.Linear wrt its input); w is read in its forward storage */
@@ -441,7 +441,8 @@ int pdf_mano_split_coeff_bwd(const float* params, float* dparams, int ldp, long 
  *                        then computed in the Winograd domain (csrc/winograd.hip): F(4x4, 3x3) -- 36 planes, 4x fewer multiplications, ~4e-5 absolute
  *                        error on values of a few units -- where the map edges are multiples of 4 and PDF_WINOGRAD_F4 (bit mask, default 15 = every
  *                        launch) permits, else F(2x2, 3x3) (16 planes, 2.25x fewer, MORE accurate than the direct fp32 sum); the weight gradient is
- *                        taken in the transform domain too (backward = 2).  PDF_WINOGRAD=2: F(2x2) only; =0: the direct kernels.  *   wino_v               pdf_conv2d_bwd_weight (Winograd F(4x4) path): the transformed input V [36][tiles][Cin] that the FORWARD of the same
+ *                        taken in the transform domain too (backward = 2).  PDF_WINOGRAD=2: F(2x2) only; =0: the direct kernels.
+ *   wino_v               pdf_conv2d_bwd_weight (Winograd F(4x4) path): the transformed input V [36][tiles][Cin] that the FORWARD of the same
  *                        convolution left in its workspace (at float offset pdf_conv2d_winograd_v_offset(...) of the forward `ws`): the
  *                        weight gradient then skips its own input transform (same kernel, same values).  The caller keeps that workspace
  *                        alive and unmodified from the forward to the weight-gradient call.
@@ -449,16 +450,16 @@ int pdf_mano_split_coeff_bwd(const float* params, float* dparams, int ldp, long 
  *                        heads reading one feature map): this forward skips its input transform.  V depends on (x, N, H, W, Cin) only.
  */
 typedef struct PdfCallOpts {
-    const void* op0_bf16; const void* op1_bf16;
-    void* out_bf16;
-    const void* bn_x_bf16;
-    float* stats_out; long stats_cap;
-    long stats_tiles; long stats_rows;
-    const float* tile_stats; long tile_n; long tile_rows;
-    const float* in_scale; const float* in_shift;
-    const void* op1_bf16_t;
-    float* ws; long ws_floats;
-    const float* wino_v;
+    const void* op0_bf16; const void* op1_bf16;      /* bf16 shadows of the call's two operands (GEMM family) */
+    void* out_bf16;                                  /* bf16 shadow of the output, or the bf16-only output (storage mode) */
+    const void* bn_x_bf16;                           /* BatchNorm: x as bf16 instead of the fp32 pointer */
+    float* stats_out; long stats_cap;                /* conv / linear forward: BatchNorm statistics of the output from the epilogue */
+    long stats_tiles; long stats_rows;               /* OUT: row blocks / rows per block written to stats_out (0: none) */
+    const float* tile_stats; long tile_n; long tile_rows;  /* BatchNorm: such partials instead of its own statistics pass */
+    const float* in_scale; const float* in_shift;    /* x read as relu(x * scale[k] + shift[k]) (linear fwd / weight gradient) */
+    const void* op1_bf16_t;                          /* backward-data: the weight's TRANSPOSED bf16 shadow wt[c][tap][r] (pdf_cast_bf16_transposed) */
+    float* ws; long ws_floats;                       /* conv2d forward / backward-data / weight gradient: workspace of pdf_conv2d_winograd_workspace_floats -> Winograd path */
+    const float* wino_v;                             /* conv2d weight gradient: the forward's transformed input (pdf_conv2d_winograd_v_offset into ITS ws) */
 } PdfCallOpts;
 /* float offset of V inside the forward workspace of this convolution, or -1 when its forward is not an F(4x4) launch (no V the weight gradient could take) */
 long pdf_conv2d_winograd_v_offset(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
@@ -479,12 +480,12 @@ int pdf_bn_train_fwd_x(const float* x, int ldx, int C, long R, const float* gamm
 int pdf_bn_train_bwd_x(const float* dy, int lddy, const float* y, int ldy, int relu, const float* x, int ldx, const float* save_mean, const float* save_rstd, const float* gamma, const float* scale, const float* shift, int C, long R, float* dx, int lddx, float* dres, int lddr, float* dgamma, float* dbeta, int accumulate, float* ws, void* stream, PdfCallOpts* opts);
 int pdf_bn_relu_maxk_fwd_x(const float* y, int ldy, int C, long R, int K, const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum, float eps, int training, float* out, int ldo, int* arg, float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, void* stream, PdfCallOpts* opts);
 int pdf_l2norm_cat_fwd_x(int nparts, const float* const* x, const int* C, const float* const* w, float eps, long R, float* y, int ldy, float* const* norm, void* stream, PdfCallOpts* opts);
-/* number of hand-over slots currently armed on the calling thread (0 after every entry-point call), and sizeof(PdfCallOpts) as the
- * library was built (a binding checks its own layout against it) */
 /* Winograd F(4x4, 3x3) / F(2x2, 3x3) for stride-1 3x3 convolutions with >= 128 input channels (nn.Conv2d sites intaghand_encoder.py:602,617,
  * 675-693, 270-316 and ResNet layers 2-3; selection rule: PdfCallOpts::ws above): floats of workspace the layer wants (PdfCallOpts::ws) for its
  * forward (backward = 0), backward-data (1) or weight-gradient (2) pass, 0 when it does not qualify.  `feat` at B = 32: ~1.5 GB per pass. */
 long pdf_conv2d_winograd_workspace_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int backward);
+/* number of hand-over slots currently armed on the calling thread (0 after every entry-point call), and sizeof(PdfCallOpts) as the
+ * library was built (a binding checks its own layout against it) */
 int pdf_debug_armed_slots(void);
 int pdf_debug_callopts_size(void);
 
@@ -531,33 +532,35 @@ int pdf_batched_gemm_tn(const float* P, const float* Q, float* slab, int batch, 
  * weight-gradient GEMMs on `side_stream`, which first waits for `stream`), and uses `gtape` (pdf_mesh_gtape_floats) and `wg_ws`
  * (>= 2 * pdf_wgrad_workspace_floats(B * V, C, 4 * C) floats) as scratch.  Dropout masks are the stateless hash of (seed, element index)
  * the unfused kernels use, so the same seeds give the same masks. */
-typedef struct PdfMeshLin { const float* w[2]; const float* b[2]; } PdfMeshLin;
+typedef struct PdfMeshLin { const float* w[2]; const float* b[2]; } PdfMeshLin;            /* [hand] */
 typedef struct PdfMeshLN { const float* g[2]; const float* b[2]; } PdfMeshLN;
 typedef struct PdfMeshGcn { PdfMeshLin fc1, fc2, sc; PdfMeshLN n2, n3; unsigned long long seed; } PdfMeshGcn;
 typedef struct PdfMeshAttn {
     PdfMeshLN ln; PdfMeshLin q, k, v, fc; PdfMeshLN ffln; PdfMeshLin f1, f2;
     unsigned long long seed_att, seed_z, seed_t, seed_x;
 } PdfMeshAttn;
+/* gradient outputs (accumulated, += ): same shapes as the parameters */
 typedef struct PdfMeshLinG { float* w[2]; float* b[2]; } PdfMeshLinG;
 typedef struct PdfMeshLNG { float* g[2]; float* b[2]; } PdfMeshLNG;
 typedef struct PdfMeshGcnG { PdfMeshLinG fc1, fc2, sc; PdfMeshLNG n2, n3; } PdfMeshGcnG;
 typedef struct PdfMeshAttnG { PdfMeshLNG ln; PdfMeshLinG q, k, v, fc; PdfMeshLNG ffln; PdfMeshLinG f1, f2; } PdfMeshAttnG;
 typedef struct PdfMeshLevel {
-    int level, B, training, cin0;
-    float p;
-    const unsigned long long* step;
-    const float* x;
-    float* out;
+    int level, B, training, cin0;                 /* level 0..2 (V = 63 << level, C = 256 >> level); cin0 = width of x (= 2 C) */
+    float p;                                      /* dropout probability (0 in eval mode) */
+    const unsigned long long* step;               /* device step counter mixed into every dropout seed (hipGraph replays draw fresh masks) */
+    const float* x;                               /* [2][B][V][cin0] level input (position embedding already added) */
+    float* out;                                   /* [2][B][V][C] level output */
     const int* ell_col[2]; const float* ell_val[2]; const int* ell_colT[2]; const float* ell_valT[2]; int ell_w;
     PdfMeshGcn gcn[4];
     PdfMeshAttn self_, cross;
-    float* tape;
-    float* qkv;
-    const float* dout;
-    float* dx;
-    float* gtape;
+    float* tape;                                  /* training: pdf_mesh_tape_floats(level, B) floats (forward writes, backward reads) */
+    float* qkv;                                   /* [3][2][B][V][C] cross-hand q / k / v (part 1 -> part 2; also part of the tape) */
+    /* backward */
+    const float* dout;                            /* [2][B][V][C] */
+    float* dx;                                    /* [2][B][V][cin0] */
+    float* gtape;                                 /* pdf_mesh_gtape_floats(level, B) floats: the dY operands of the weight-gradient GEMMs */
     PdfMeshGcnG ggcn[4]; PdfMeshAttnG gself, gcross;
-    float* wg_ws; long wg_ws_floats;
+    float* wg_ws; long wg_ws_floats;              /* workspace of the weight-gradient launches */
 } PdfMeshLevel;
 long pdf_mesh_tape_floats(int level, int B);
 long pdf_mesh_gtape_floats(int level, int B);
@@ -581,15 +584,16 @@ int pdf_debug_mesh_level_size(void);
  * `valid` and x1000 where the reference does, :506-525), then the per-sample weighted sum of the twelve with `coef` (the reference's :610-640
  * weights, same order).  The backward writes the gradients of sum_b gmp[b] * weighted_sum[b]. */
 typedef struct PdfMeshLoss {
-    const float* vp; const float* v2p; const float* hd3; const float* hd2; const float* r;
-    const float* vgt[2]; const float* jgt[2]; const float* v2gt[2]; const float* lmsgt[2];     /* ground truth per hand, [B][...] each */
-    const long long* ind; const float* K; const float* valid;
-    const float* reg[2]; const long long* faces; const long long* perm[2];
+    const float* vp; const float* v2p; const float* hd3; const float* hd2; const float* r;      /* predictions [2][B][...] */
+    const float* vgt[2]; const float* jgt[2]; const float* v2gt[2]; const float* lmsgt[2];     /* ground truth per hand [B][...] (the batch's own tensors) */
+    const long long* ind; const float* K; const float* valid;                                  /* [B][2] i64, [B][3][3], [B][2] */
+    const float* reg[2]; const long long* faces; const long long* perm[2];                     /* [21][778] x 2, [2][F][3], [1008] x 2 */
     int B, Fc, size, down;
-    float* part;
-    float* out;
-    float coef[12];
-    const float* gmp;
+    float* part;                                                                               /* [2][B][12] */
+    float* out;                                                                                /* forward: 4 + 9 B floats, see above */
+    float coef[12];                                                                            /* weights of the reference's sum (:610-640), order of `out` */
+    /* backward */
+    const float* gmp;                                                                          /* [B] upstream gradient of the weighted sum out[4 + 8 B ..] */
     int edge_grad;
     float* dvp; float* dv2p; float* dhd3; float* dhd2; float* dr;
 } PdfMeshLoss;

@@ -2,12 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pdfnet_hip.h"      // the public contract: every PDF_API definition below is compiled against its prototype, the argument blocks are its structs
 
+// Every entry point returns 0 on success or a negative PDF_E_* / positive hipError_t code (pdfnet_hip.h).
 #define PDF_API extern "C" __attribute__((visibility("default")))
-
-// Every entry point returns 0 on success or a negative PDF_E_* / positive hipError_t code.
-#define PDF_E_BADARG (-1)
-#define PDF_E_WORKSPACE (-2)
 
 #define PDF_LAUNCH_CHECK()                                  \
     do {                                                    \
@@ -122,21 +120,8 @@ __device__ __forceinline__ void pdf_x3_store2(unsigned short* base, long o, long
     *reinterpret_cast<unsigned*>(base + o + cs) = m;
     *reinterpret_cast<unsigned*>(base + o + 2 * cs) = l;
 }
-// Everything a call may take beyond its positional arguments -- must match `PdfCallOpts` of include/pdfnet_hip.h field for field
-// (tests/c_abi/c_client.c compares sizeof with pdf_debug_callopts_size()).  The `_x` form of an entry point takes it explicitly; the
+// PdfCallOpts (pdfnet_hip.h): everything a call may take beyond its positional arguments.  The `_x` form of an entry point takes it explicitly; the
 // plain form takes (and clears) the thread's hand-over slots FIRST THING, so no return path leaves a slot armed.
-struct PdfCallOpts {
-    const void* op0_bf16; const void* op1_bf16;     // bf16 shadows of the call's two operands (GEMM family)
-    void* out_bf16;                                  // bf16 shadow of the output, or the bf16-only output (storage mode)
-    const void* bn_x_bf16;                           // BatchNorm: x as bf16 instead of the fp32 pointer
-    float* stats_out; long stats_cap;                // conv / linear forward: BatchNorm statistics of the output from the epilogue
-    long stats_tiles, stats_rows;                    // OUT: row blocks / rows per block written to stats_out (0: none)
-    const float* tile_stats; long tile_n, tile_rows; // BatchNorm: such partials instead of its own statistics pass
-    const float* in_scale; const float* in_shift;    // x read as relu(x * scale[k] + shift[k]) (linear fwd / weight gradient)
-    const void* op1_bf16_t;                          // backward-data: the weight's TRANSPOSED bf16 shadow wt[c][tap][r] (pdf_cast_bf16_transposed)
-    float* ws; long ws_floats;                       // conv2d forward / backward-data / weight gradient: workspace of pdf_conv2d_winograd_workspace_floats -> Winograd path
-    const float* wino_v;                             // conv2d weight gradient: the forward's transformed input (pdf_conv2d_winograd_v_offset into ITS ws)
-};
 PdfCallOpts pdf_tls_take_all();                      // the thread's armed slots, cleared
 void pdf_tls_publish(const PdfCallOpts& o);          // stats_tiles / stats_rows -> pdf_stats_result_*
 

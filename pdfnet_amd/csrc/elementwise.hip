@@ -12,7 +12,8 @@ __global__ void act_fwd_kernel(const float* __restrict__ x, int ldx, float* __re
         y[r * ldy + c] = act == 1 ? fmaxf(v, 0.f) : (v > 0.f ? v : 0.1f * v);
     }
 }
-PDF_API int pdf_act_fwd(const float* x, int ldx, float* y, int ldy, int C, long R, int act, hipStream_t s) {
+PDF_API int pdf_act_fwd(const float* x, int ldx, float* y, int ldy, int C, long R, int act, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R * C <= 0) return 0;
     hipLaunchKernelGGL(act_fwd_kernel, dim3(grid_for(R * C)), dim3(256), 0, s, x, ldx, y, ldy, C, R * C, act);
     PDF_LAUNCH_CHECK();
@@ -29,7 +30,8 @@ __global__ void act_bwd_kernel(const float* __restrict__ dy, int lddy, const flo
         dx[r * lddx + c] = pos ? g : (act == 1 ? 0.f : 0.1f * g);
     }
 }
-PDF_API int pdf_act_bwd(const float* dy, int lddy, const float* y, int ldy, float* dx, int lddx, int C, long R, int act, hipStream_t s) {
+PDF_API int pdf_act_bwd(const float* dy, int lddy, const float* y, int ldy, float* dx, int lddx, int C, long R, int act, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R * C <= 0) return 0;
     hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(R * C)), dim3(256), 0, s, dy, lddy, y, ldy, dx, lddx, C, R * C, act);
     PDF_LAUNCH_CHECK();
@@ -45,7 +47,8 @@ __global__ void sft_fwd_kernel(const float* __restrict__ fea, int ldf, const flo
     }
 }
 PDF_API int pdf_sft_fwd(const float* fea, int ldf, const float* scale, int lds_, const float* shift, int ldh,
-                        float* out, int ldo, int C, long R, hipStream_t s) {
+                        float* out, int ldo, int C, long R, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R * C <= 0) return 0;
     hipLaunchKernelGGL(sft_fwd_kernel, dim3(grid_for(R * C)), dim3(256), 0, s, fea, ldf, scale, lds_, shift, ldh, out, ldo, C, R * C);
     PDF_LAUNCH_CHECK();
@@ -62,7 +65,8 @@ __global__ void sft_bwd_kernel(const float* __restrict__ g, int ldg, const float
     }
 }
 PDF_API int pdf_sft_bwd(const float* g, int ldg, const float* fea, int ldf, const float* scale, int lds_,
-                        float* dfea, int lddf, float* dscale, int ldds, int C, long R, hipStream_t s) {
+                        float* dfea, int lddf, float* dscale, int ldds, int C, long R, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R * C <= 0) return 0;
     hipLaunchKernelGGL(sft_bwd_kernel, dim3(grid_for(R * C)), dim3(256), 0, s, g, ldg, fea, ldf, scale, lds_, dfea, lddf, dscale, ldds, C, R * C);
     PDF_LAUNCH_CHECK();
@@ -94,7 +98,8 @@ __global__ __launch_bounds__(256) void sft3_fwd_kernel(const float* __restrict__
 }
 PDF_API int pdf_sft3_fwd(const float* fea, int ldf, const float* cond, int ldc, const float* w_scale0, const float* b_scale0,
                          const float* w_scale1, const float* b_scale1, const float* w_shift0, const float* b_shift0,
-                         const float* w_shift1, const float* b_shift1, float* out, int ldo, long R, hipStream_t s) {
+                         const float* w_shift1, const float* b_shift1, float* out, int ldo, long R, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R <= 0) return 0;
     Sft3Params p = {{w_scale0, w_scale1, w_shift0, w_shift1}, {b_scale0, b_scale1, b_shift0, b_shift1}};
     hipLaunchKernelGGL(sft3_fwd_kernel, dim3(grid_for(R)), dim3(256), 0, s, fea, ldf, cond, ldc, p, out, ldo, R);
@@ -187,7 +192,8 @@ PDF_API int pdf_sft3_bwd(const float* g, int ldg, const float* fea, int ldf, con
                          float* dfea, int lddf, float* dcond, int lddc,
                          float* dw_scale0, float* db_scale0, float* dw_scale1, float* db_scale1,
                          float* dw_shift0, float* db_shift0, float* dw_shift1, float* db_shift1, int accumulate,
-                         float* ws, long R, hipStream_t s) {
+                         float* ws, long R, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R <= 0) return 0;
     Sft3Params p = {{w_scale0, w_scale1, w_shift0, w_shift1}, {b_scale0, b_scale1, b_shift0, b_shift1}};
     Sft3Grads d = {{dw_scale0, dw_scale1, dw_shift0, dw_shift1}, {db_scale0, db_scale1, db_shift0, db_shift1}};
@@ -206,7 +212,8 @@ __global__ void dropout_kernel(const float* __restrict__ x, float* __restrict__ 
     if (step != nullptr) seed += step[0] * 0x9E3779B97F4A7C15ull;      // per-step stream under hipGraph replay
     GRID_STRIDE(i, n) y[i] = pdf_uniform(seed, (unsigned long long)i) >= p ? x[i] * sc : 0.f;
 }
-PDF_API int pdf_dropout(const float* x, float* y, long n, float p, unsigned long long seed, const unsigned long long* step, hipStream_t s) {
+PDF_API int pdf_dropout(const float* x, float* y, long n, float p, unsigned long long seed, const unsigned long long* step, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (n <= 0) return 0;
     hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, y, n, p, seed, step);
     PDF_LAUNCH_CHECK();
@@ -221,7 +228,8 @@ __global__ void dropout_add_kernel(const float* __restrict__ x, const float* __r
     GRID_STRIDE(i, n) y[i] = res[i] + ((p <= 0.f || pdf_uniform(seed, (unsigned long long)i) >= p) ? x[i] * sc : 0.f);
 }
 PDF_API int pdf_dropout_add(const float* x, const float* res, float* y, long n, float p, unsigned long long seed,
-                            const unsigned long long* step, hipStream_t s) {
+                            const unsigned long long* step, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (n <= 0) return 0;
     hipLaunchKernelGGL(dropout_add_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, res, y, n, p, seed, step);
     PDF_LAUNCH_CHECK();
@@ -279,7 +287,8 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd_v4_kernel(const float* __r
         *reinterpret_cast<uchar4*>(arg + i * 4) = make_uchar4((unsigned char)b0, (unsigned char)b1, (unsigned char)b2, (unsigned char)b3);
     }
 }
-PDF_API int pdf_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, float* y, unsigned char* arg, hipStream_t s) {
+PDF_API int pdf_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, float* y, unsigned char* arg, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
     long total = (long)N * OH * OW * C;
     if (total <= 0) return 0;
@@ -346,12 +355,14 @@ static int maxpool3s2_bwd(const float* dy, const unsigned char* arg, int N, int 
     PDF_LAUNCH_CHECK();
     return 0;
 }
-PDF_API int pdf_maxpool3s2_bwd(const float* dy, const unsigned char* arg, int N, int H, int W, int C, float* dx, hipStream_t s) {
+PDF_API int pdf_maxpool3s2_bwd(const float* dy, const unsigned char* arg, int N, int H, int W, int C, float* dx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return maxpool3s2_bwd(dy, arg, N, H, W, C, dx, 0, s);
 }
 // dx += the same: dx already holds the gradient of the input's other consumers (the stem output also feeds the PointNet++ row
 // gathers) -- one pass instead of a separate add over both tensors.  (The atomic fallback accumulates by construction.)
-PDF_API int pdf_maxpool3s2_bwd_add(const float* dy, const unsigned char* arg, int N, int H, int W, int C, float* dx, hipStream_t s) {
+PDF_API int pdf_maxpool3s2_bwd_add(const float* dy, const unsigned char* arg, int N, int H, int W, int C, float* dx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return maxpool3s2_bwd(dy, arg, N, H, W, C, dx, 1, s);
 }
 
@@ -404,7 +415,8 @@ static bool up2_v4_ok(const void* a, const void* b, int N, int H, int W, int C) 
     return C % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0 && (long)N * 2 * H < 65536 &&
            (long)2 * W * (C / 4) < (1L << 30);
 }
-PDF_API int pdf_upsample2x_fwd(const float* x, int N, int H, int W, int C, float* y, hipStream_t s) {
+PDF_API int pdf_upsample2x_fwd(const float* x, int N, int H, int W, int C, float* y, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)N * 4 * H * W * C;
     if (total <= 0) return 0;
     if (up2_v4_ok(x, y, N, H, W, C)) {
@@ -482,7 +494,8 @@ __global__ __launch_bounds__(256) void up2_bwd_gather_kernel(const float* __rest
         for (int b = 0; b < nx; ++b) acc += wys[a] * wxs[b] * g[((long)oys[a] * OW + oxs[b]) * C];
     dx[((long)blockIdx.y * W + ix) * C + c] = acc;
 }
-PDF_API int pdf_upsample2x_bwd(const float* dy, int N, int H, int W, int C, float* dx, hipStream_t s) {
+PDF_API int pdf_upsample2x_bwd(const float* dy, int N, int H, int W, int C, float* dx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)N * 4 * H * W * C;
     if (total <= 0) return 0;
     if (up2_v4_ok(dy, dx, N, H, W, C)) {
@@ -514,7 +527,8 @@ __global__ void pad2d_kernel(const float* __restrict__ src, int lds, long R, int
         dst[r * ldd + c] = (r < R && c < C) ? src[r * lds + c] : 0.f;
     }
 }
-PDF_API int pdf_pad2d(const float* src, int lds, long R, int C, float* dst, int ldd, long R2, int C2, hipStream_t s) {
+PDF_API int pdf_pad2d(const float* src, int lds, long R, int C, float* dst, int ldd, long R2, int C2, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R < 0 || C < 0 || R2 < 0 || C2 < 0 || lds < C || ldd < C2) return PDF_E_BADARG;
     if (R2 == 0 || C2 == 0) return 0;
     hipLaunchKernelGGL(pad2d_kernel, dim3(grid_for(R2 * C2)), dim3(256), 0, s, src, lds, R, C, dst, ldd, R2, C2);
@@ -539,7 +553,8 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     }
 }
 PDF_API int pdf_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
-                          const float* corr, float grad_scale, hipStream_t s) {
+                          const float* corr, float grad_scale, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (n <= 0) return 0;
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, corr, grad_scale);
     PDF_LAUNCH_CHECK();
@@ -619,7 +634,8 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
         reinterpret_cast<uint2*>(dst)[i] = uint2{pdf_pk_bf16(v.x, v.y), pdf_pk_bf16(v.z, v.w)};
     }
 }
-PDF_API int pdf_cast_bf16(const float* src, void* dst, long n, hipStream_t s) {
+PDF_API int pdf_cast_bf16(const float* src, void* dst, long n, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (n <= 0) return 0;
     if (n % 4 != 0) return PDF_E_BADARG;
     hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n / 4)), dim3(256), 0, s, src, reinterpret_cast<unsigned short*>(dst), n / 4);
@@ -661,7 +677,8 @@ __global__ __launch_bounds__(256) void cast_bf16_t_kernel(const float* __restric
         if (r < d.R && c < d.C) dp[((long)c * d.T + tap) * d.R + r] = (unsigned short)(pdf_pk_bf16(tile[tx][ty + 8 * i], 0.f) & 0xffffu);
     }
 }
-PDF_API int pdf_cast_bf16_transposed(const float* src, void* dst, const void* table, int nlayers, long total_tiles, hipStream_t s) {
+PDF_API int pdf_cast_bf16_transposed(const float* src, void* dst, const void* table, int nlayers, long total_tiles, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (nlayers <= 0 || total_tiles <= 0) return 0;
     if (total_tiles > 0x7fffffffL) return PDF_E_BADARG;
     hipLaunchKernelGGL(cast_bf16_t_kernel, dim3((unsigned)total_tiles), dim3(256), 0, s, src, reinterpret_cast<unsigned short*>(dst),
@@ -687,7 +704,8 @@ static int pdf_event_ring(void) {
 }
 // `waiter` waits for everything `signaler` has been given so far.  A wait captures the event's latest record when it is
 // issued, so re-recording a ring slot later does not disturb it.
-PDF_API int pdf_stream_wait(hipStream_t waiter, hipStream_t signaler) {
+PDF_API int pdf_stream_wait(void* waiter_stream, void* signaler_stream) {
+    hipStream_t waiter = (hipStream_t)waiter_stream, signaler = (hipStream_t)signaler_stream;
     if (waiter == signaler) return 0;
     if (int rc = pdf_event_ring()) return rc;
     hipEvent_t e = g_events[g_event_next.fetch_add(1, std::memory_order_relaxed) % PDF_EVENT_RING];

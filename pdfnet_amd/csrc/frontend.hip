@@ -160,7 +160,8 @@ __global__ __launch_bounds__(FE_T) void depth2pcl_kernel(const float* __restrict
 }
 
 PDF_API int pdf_depth2pcl(const float* depth, const float* mask, const float* K, const float* valid, int B, int H, int W,
-                          unsigned long long seed, long* choose, float* cloud, int* count, hipStream_t s) {
+                          unsigned long long seed, long* choose, float* cloud, int* count, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     hipLaunchKernelGGL(depth2pcl_kernel, dim3(2 * B), dim3(FE_T), 0, s, depth, mask, K, valid, H, W, seed, choose, cloud, count);
     PDF_LAUNCH_CHECK();

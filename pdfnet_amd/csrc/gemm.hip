@@ -1611,9 +1611,9 @@ static int pdf_linear_fwd_impl(const float* x, const float* w, const float* bias
     return launch_igemm(g, s, 1, sr.cap);
 }
 PDF_API int pdf_linear_fwd_x(const float* x, const float* w, const float* bias, float* y,
-                           int M, int N, int K, int ldx, int ldw, int ldy, int act, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_fwd_impl(x, w, bias, y, M, N, K, ldx, ldw, ldy, act, s, co); }
+                           int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_fwd_impl(x, w, bias, y, M, N, K, ldx, ldw, ldy, act, s, co); }
 PDF_API int pdf_linear_fwd(const float* x, const float* w, const float* bias, float* y,
-                           int M, int N, int K, int ldx, int ldw, int ldy, int act, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_fwd_impl(x, w, bias, y, M, N, K, ldx, ldw, ldy, act, s, co); pdf_tls_publish(co); return rc; }
+                           int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_fwd_impl(x, w, bias, y, M, N, K, ldx, ldw, ldy, act, s, co); pdf_tls_publish(co); return rc; }
 
 // Two same-shaped layers with their own parameters in ONE launch (the left / right hand branches of the mesh decoder,
 // DualGraph.py:83-84, inter_attn.py:66-67): rows [0, M) of x / y belong to (w0, b0), rows [M, 2M) to (w1, b1).
@@ -1624,9 +1624,9 @@ static int pdf_linear_fwd_pair_impl(const float* x, const float* w0, const float
     return launch_igemm(g, s, 2);
 }
 PDF_API int pdf_linear_fwd_pair_x(const float* x, const float* w0, const float* w1, const float* b0, const float* b1, float* y,
-                                int M, int N, int K, int ldx, int ldw, int ldy, int act, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_fwd_pair_impl(x, w0, w1, b0, b1, y, M, N, K, ldx, ldw, ldy, act, s, co); }
+                                int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_fwd_pair_impl(x, w0, w1, b0, b1, y, M, N, K, ldx, ldw, ldy, act, s, co); }
 PDF_API int pdf_linear_fwd_pair(const float* x, const float* w0, const float* w1, const float* b0, const float* b1, float* y,
-                                int M, int N, int K, int ldx, int ldw, int ldy, int act, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_fwd_pair_impl(x, w0, w1, b0, b1, y, M, N, K, ldx, ldw, ldy, act, s, co); pdf_tls_publish(co); return rc; }
+                                int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_fwd_pair_impl(x, w0, w1, b0, b1, y, M, N, K, ldx, ldw, ldy, act, s, co); pdf_tls_publish(co); return rc; }
 
 // dx[M][K] = dy[M][N] w[N][K]: the weight is read in its forward [N][K] storage (no transposed copy)
 static int pdf_linear_bwd_data_impl(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int ldw, int lddx,
@@ -1639,9 +1639,9 @@ static int pdf_linear_bwd_data_impl(const float* dy, const float* w, float* dx, 
     return launch_igemm(g, s);
 }
 PDF_API int pdf_linear_bwd_data_x(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int ldw, int lddx,
-                                hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_data_impl(dy, w, dx, M, N, K, lddy, ldw, lddx, s, co); }
+                                void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_data_impl(dy, w, dx, M, N, K, lddy, ldw, lddx, s, co); }
 PDF_API int pdf_linear_bwd_data(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int ldw, int lddx,
-                                hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_data_impl(dy, w, dx, M, N, K, lddy, ldw, lddx, s, co); pdf_tls_publish(co); return rc; }
+                                void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_data_impl(dy, w, dx, M, N, K, lddy, ldw, lddx, s, co); pdf_tls_publish(co); return rc; }
 
 static int pdf_linear_bwd_data_pair_impl(const float* dy, const float* w0, const float* w1, float* dx, int M, int N, int K,
                                      int lddy, int ldw, int lddx, hipStream_t s, PdfCallOpts& co) {
@@ -1651,9 +1651,9 @@ static int pdf_linear_bwd_data_pair_impl(const float* dy, const float* w0, const
     return launch_igemm(g, s, 2);
 }
 PDF_API int pdf_linear_bwd_data_pair_x(const float* dy, const float* w0, const float* w1, float* dx, int M, int N, int K,
-                                     int lddy, int ldw, int lddx, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_data_pair_impl(dy, w0, w1, dx, M, N, K, lddy, ldw, lddx, s, co); }
+                                     int lddy, int ldw, int lddx, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_data_pair_impl(dy, w0, w1, dx, M, N, K, lddy, ldw, lddx, s, co); }
 PDF_API int pdf_linear_bwd_data_pair(const float* dy, const float* w0, const float* w1, float* dx, int M, int N, int K,
-                                     int lddy, int ldw, int lddx, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_data_pair_impl(dy, w0, w1, dx, M, N, K, lddy, ldw, lddx, s, co); pdf_tls_publish(co); return rc; }
+                                     int lddy, int ldw, int lddx, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_data_pair_impl(dy, w0, w1, dx, M, N, K, lddy, ldw, lddx, s, co); pdf_tls_publish(co); return rc; }
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1924,10 +1924,10 @@ static int pdf_conv2d_fwd_impl(const float* x, const float* w, const float* bias
 }
 PDF_API int pdf_conv2d_fwd_x(const float* x, const float* w, const float* bias, float* y,
                            int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                           int stride, int pad, int OH, int OW, int ldy, int act, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, act, s, co); }
+                           int stride, int pad, int OH, int OW, int ldy, int act, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, act, s, co); }
 PDF_API int pdf_conv2d_fwd(const float* x, const float* w, const float* bias, float* y,
                            int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                           int stride, int pad, int OH, int OW, int ldy, int act, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, act, s, co); pdf_tls_publish(co); return rc; }
+                           int stride, int pad, int OH, int OW, int ldy, int act, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, act, s, co); pdf_tls_publish(co); return rc; }
 
 
 // Conv2d backward-data: dx[N,H,W,Cin] from dy[N,OH,OW,Cout] and the FORWARD weight w = [Cout][KH][KW][Cin], read as
@@ -1989,10 +1989,10 @@ static int pdf_conv2d_bwd_data_impl(const float* dy, const float* w, float* dx,
 }
 PDF_API int pdf_conv2d_bwd_data_x(const float* dy, const float* w, float* dx,
                                 int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                int stride, int pad, int OH, int OW, int lddy, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
+                                int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
 PDF_API int pdf_conv2d_bwd_data(const float* dy, const float* w, float* dx,
                                 int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                int stride, int pad, int OH, int OW, int lddy, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
+                                int stride, int pad, int OH, int OW, int lddy, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
 
 // dx += the same (stride 1): the gradient of a tensor with two consumers -- a ResNet block input feeds conv1 and the shortcut --
 // is accumulated by the second producer's epilogue instead of a separate add pass over both gradients
@@ -2003,10 +2003,10 @@ static int pdf_conv2d_bwd_data_add_impl(const float* dy, const float* w, float* 
 }
 PDF_API int pdf_conv2d_bwd_data_add_x(const float* dy, const float* w, float* dx,
                                     int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_data_add_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
+                                    int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_data_add_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
 PDF_API int pdf_conv2d_bwd_data_add(const float* dy, const float* w, float* dx,
                                     int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_data_add_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
+                                    int stride, int pad, int OH, int OW, int lddy, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_data_add_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
 
 
 // Split count of a weight-gradient launch: the candidate with the smallest modelled time (see launch_wgemm).
@@ -2202,9 +2202,9 @@ static int pdf_linear_bwd_weight_impl(const float* x, const float* dy, float* dw
     return launch_wgemm(g, dw, ws, ws_floats, accumulate, s, nullptr, db);
 }
 PDF_API int pdf_linear_bwd_weight_x(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
-                                  int M, int N, int K, int ldx, int lddy, int accumulate, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); }
+                                  int M, int N, int K, int ldx, int lddy, int accumulate, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); }
 PDF_API int pdf_linear_bwd_weight(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
-                                  int M, int N, int K, int ldx, int lddy, int accumulate, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
+                                  int M, int N, int K, int ldx, int lddy, int accumulate, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
 
 
 // paired form of the above: rows [0, M) -> dw0, rows [M, 2M) -> dw1; ws >= 2 * pdf_wgrad_workspace_floats(M, N, K)
@@ -2218,9 +2218,9 @@ static int pdf_linear_bwd_weight_pair_impl(const float* x, const float* dy, floa
     return launch_wgemm(g, dw0, ws, ws_floats, accumulate, s, dw1, db0, db1);
 }
 PDF_API int pdf_linear_bwd_weight_pair_x(const float* x, const float* dy, float* dw0, float* dw1, float* db0, float* db1,
-                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_weight_pair_impl(x, dy, dw0, dw1, db0, db1, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); }
+                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_weight_pair_impl(x, dy, dw0, dw1, db0, db1, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); }
 PDF_API int pdf_linear_bwd_weight_pair(const float* x, const float* dy, float* dw0, float* dw1, float* db0, float* db1,
-                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_weight_pair_impl(x, dy, dw0, dw1, db0, db1, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
+                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_weight_pair_impl(x, dy, dw0, dw1, db0, db1, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
 
 
 // dW[Cout][KH][KW][Cin] (+)= sum over output pixels dy[m][co] * x[pos(m,tap)][ci]
@@ -2391,10 +2391,10 @@ static int pdf_conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw
 }
 PDF_API int pdf_conv2d_bwd_weight_x(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
                                   int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); }
+                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); }
 PDF_API int pdf_conv2d_bwd_weight(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
                                   int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
+                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
 
 
 // ConvTranspose2d forward on NHWC: y[n, iy*s - pad + ky, ix*s - pad + kx, co] += x[n,iy,ix,ci] w[ci][co][ky][kx].
@@ -2459,10 +2459,10 @@ static int pdf_deconv2d_fwd_impl(const float* x, const float* w, const float* bi
 }
 PDF_API int pdf_deconv2d_fwd_x(const float* x, const float* w, const float* bias, float* y,
                              int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                             int stride, int pad, int OH, int OW, int ldy, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, s, co); }
+                             int stride, int pad, int OH, int OW, int ldy, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, s, co); }
 PDF_API int pdf_deconv2d_fwd(const float* x, const float* w, const float* bias, float* y,
                              int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                             int stride, int pad, int OH, int OW, int ldy, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, s, co); pdf_tls_publish(co); return rc; }
+                             int stride, int pad, int OH, int OW, int ldy, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, s, co); pdf_tls_publish(co); return rc; }
 
 
 // ConvTranspose2d backward-data: dx[n,iy,ix,ci] = sum dy[n, iy*s-pad+ky, ix*s-pad+kx, co] w[ci][ky][kx][co]
@@ -2490,10 +2490,10 @@ static int pdf_deconv2d_bwd_data_impl(const float* dy, const float* w, float* dx
 }
 PDF_API int pdf_deconv2d_bwd_data_x(const float* dy, const float* w, float* dx,
                                   int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
+                                  int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
 PDF_API int pdf_deconv2d_bwd_data(const float* dy, const float* w, float* dx,
                                   int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
+                                  int stride, int pad, int OH, int OW, int lddy, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
 
 
 // ConvTranspose2d weight gradient in the natural [Cin][KH][KW][Cout] storage.
@@ -2523,8 +2523,8 @@ static int pdf_deconv2d_bwd_weight_impl(const float* x, const float* dy, float* 
 }
 PDF_API int pdf_deconv2d_bwd_weight_x(const float* x, const float* dy, float* dw, float* ws, long ws_floats,
                                     int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_bwd_weight_impl(x, dy, dw, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); }
+                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_bwd_weight_impl(x, dy, dw, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); }
 PDF_API int pdf_deconv2d_bwd_weight(const float* x, const float* dy, float* dw, float* ws, long ws_floats,
                                     int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_bwd_weight_impl(x, dy, dw, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
+                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_bwd_weight_impl(x, dy, dw, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
 

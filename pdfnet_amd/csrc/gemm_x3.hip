@@ -62,7 +62,8 @@ __global__ __launch_bounds__(256) void x3_split_rows_kernel(const float* __restr
         *reinterpret_cast<uint4*>(d + 2 * cs) = l;
     }
 }
-PDF_API int pdf_x3_split(const float* x, void* out, long n, long cs, hipStream_t s) {
+PDF_API int pdf_x3_split(const float* x, void* out, long n, long cs, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (n % 8 != 0 || cs % 8 != 0 || ((uintptr_t)x & 15) || ((uintptr_t)out & 15)) return PDF_E_BADARG;
     hipLaunchKernelGGL(x3_split_kernel, dim3(grid_for(n / 8, 256, 256 * 16)), dim3(256), 0, s, x, (unsigned short*)out, n / 8, cs);
     PDF_LAUNCH_CHECK();
@@ -417,7 +418,8 @@ int pdf_internal_x3_batched_gemm(const void* A3, long csA, const void* B3, long 
     return x3_launch_nt<4, 2, 2, 2, 2>(g, nprod, s);
 }
 PDF_API int pdf_x3_batched_gemm_nt(const void* A3, long csA, const void* B3, long csB, float* C, int batch, long gsA, long gsB, long gsC,
-                                   int M, int N, int K, int variant, int nprod, hipStream_t s) {
+                                   int M, int N, int K, int variant, int nprod, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return pdf_internal_x3_batched_gemm(A3, csA, B3, csB, C, batch, gsA, gsB, gsC, M, N, K, variant, nprod, s);
 }
 // diagnostic builds (-DX3_STAMPS=1) only: the six stamps of the last x3gemm_nt launch (see X3_STAMPS); returns 0 otherwise
@@ -430,7 +432,8 @@ PDF_API int pdf_debug_x3_stamps(unsigned long long* out) {
 }
 int pdf_internal_batched_gemm(const float* A, const float* B, float* C, int batch, long gsA, long gsB, long gsC, int M, int N, int K, hipStream_t s);
 // the native fp32-MFMA batched product (gemm.hip) behind the same shape of call: the comparison arm of tools/x3_bench.py
-PDF_API int pdf_batched_gemm_nt(const float* A, const float* B, float* C, int batch, long gsA, long gsB, long gsC, int M, int N, int K, hipStream_t s) {
+PDF_API int pdf_batched_gemm_nt(const float* A, const float* B, float* C, int batch, long gsA, long gsB, long gsC, int M, int N, int K, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return pdf_internal_batched_gemm(A, B, C, batch, gsA, gsB, gsC, M, N, K, s);
 }
 
@@ -701,13 +704,15 @@ int pdf_internal_x3_batched_wgemm(const void* P3, long csP, const void* Q3, long
     return rc != 0 ? (rc < 0 ? rc : -rc) : g.splits;
 }
 PDF_API int pdf_x3_batched_gemm_tn(const void* P3, long csP, const void* Q3, long csQ, float* slab, int batch, long gsP, long gsQ,
-                                   int M, int NI, int NJ, int splits, int variant, int nprod, hipStream_t s) {
+                                   int M, int NI, int NJ, int splits, int variant, int nprod, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     const int rc = pdf_internal_x3_batched_wgemm(P3, csP, Q3, csQ, slab, batch, gsP, gsQ, M, NI, NJ, splits, variant, nprod, s);
     return rc > 0 ? 0 : (rc == 0 ? PDF_E_BADARG : rc);
 }
 int pdf_internal_batched_wgemm(const float* P, const float* Q, float* slab, int batch, long gsP, long gsQ, int M, int NI, int NJ, int splits, hipStream_t s);
 // the native fp32 weight-gradient-shaped batched product (gemm.hip; rows per split a multiple of 16)
-PDF_API int pdf_batched_gemm_tn(const float* P, const float* Q, float* slab, int batch, long gsP, long gsQ, int M, int NI, int NJ, int splits, hipStream_t s) {
+PDF_API int pdf_batched_gemm_tn(const float* P, const float* Q, float* slab, int batch, long gsP, long gsQ, int M, int NI, int NJ, int splits, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     const int rc = pdf_internal_batched_wgemm(P, Q, slab, batch, gsP, gsQ, M, NI, NJ, splits, s);
     return rc > 0 ? 0 : (rc == 0 ? PDF_E_BADARG : rc);
 }

@@ -26,7 +26,8 @@ __global__ void cheby2_fwd_kernel(const float* __restrict__ x, int ldx, int V, i
     }
 }
 PDF_API int pdf_cheby2_fwd(const float* x, int ldx, int B, int V, int F, const int* col, const float* val, int Wd,
-                           float* out, int ldo, hipStream_t s) {
+                           float* out, int ldo, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)B * V * F;
     if (total <= 0) return 0;
     hipLaunchKernelGGL(cheby2_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, ldx, V, F, col, val, col, val, (long)B, Wd, out, ldo, total);
@@ -35,7 +36,8 @@ PDF_API int pdf_cheby2_fwd(const float* x, int ldx, int B, int V, int F, const i
 }
 // paired: samples [0, B) with (col0, val0), samples [B, 2B) with (col1, val1)
 PDF_API int pdf_cheby2_fwd_pair(const float* x, int ldx, int B, int V, int F, const int* col0, const float* val0,
-                                const int* col1, const float* val1, int Wd, float* out, int ldo, hipStream_t s) {
+                                const int* col1, const float* val1, int Wd, float* out, int ldo, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)2 * B * V * F;
     if (total <= 0) return 0;
     hipLaunchKernelGGL(cheby2_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, ldx, V, F, col0, val0, col1, val1, (long)B, Wd, out, ldo, total);
@@ -58,7 +60,8 @@ __global__ void cheby2_bwd_kernel(const float* __restrict__ d, int ldd, int V, i
     }
 }
 PDF_API int pdf_cheby2_bwd(const float* d, int ldd, int B, int V, int F, const int* colT, const float* valT, int Wd,
-                           float* dx, int lddx, hipStream_t s) {
+                           float* dx, int lddx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)B * V * F;
     if (total <= 0) return 0;
     hipLaunchKernelGGL(cheby2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, d, ldd, V, F, colT, valT, colT, valT, (long)B, Wd, dx, lddx, total);
@@ -66,7 +69,8 @@ PDF_API int pdf_cheby2_bwd(const float* d, int ldd, int B, int V, int F, const i
     return 0;
 }
 PDF_API int pdf_cheby2_bwd_pair(const float* d, int ldd, int B, int V, int F, const int* colT0, const float* valT0,
-                                const int* colT1, const float* valT1, int Wd, float* dx, int lddx, hipStream_t s) {
+                                const int* colT1, const float* valT1, int Wd, float* dx, int lddx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)2 * B * V * F;
     if (total <= 0) return 0;
     hipLaunchKernelGGL(cheby2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, d, ldd, V, F, colT0, valT0, colT1, valT1, (long)B, Wd, dx, lddx, total);
@@ -363,7 +367,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_keys_kernel(const float* __re
     }
 
 PDF_API int pdf_attn_fwd(const float* q, const float* k, const float* v, int ld, int B, int V, int H, int dh, int kv_shift,
-                         float pdrop, unsigned long long seed, const unsigned long long* step, float* out, int ldo, float* stat, hipStream_t s) {
+                         float pdrop, unsigned long long seed, const unsigned long long* step, float* out, int ldo, float* stat, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (V <= 0) return PDF_E_BADARG;
     const int G = attn_group(V, dh), NT = cdiv(V, 256 / G);
     const bool keys = dh <= 32 && G > 1;                   // which split (see the *_keys kernels)
@@ -503,7 +508,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restric
 
 PDF_API int pdf_attn_bwd(const float* q, const float* k, const float* v, int ld, const float* o, const float* dout, int ldo,
                          const float* stat, int B, int V, int H, int dh, int kv_shift, float pdrop, unsigned long long seed, const unsigned long long* step,
-                         float* dq, float* dk, float* dv, int lddq, float* dvec, hipStream_t s) {
+                         float* dq, float* dk, float* dv, int lddq, float* dvec, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (V <= 0) return PDF_E_BADARG;
     const int G = attn_group(V, dh), NT = cdiv(V, 256 / G), RPB = 256 / G;
     const bool keys = dh <= 32 && G > 1;

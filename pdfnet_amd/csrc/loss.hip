@@ -39,7 +39,8 @@ __global__ __launch_bounds__(256) void rowloss_fwd_kernel(const float* __restric
     a = block_sum_256(a, sm);
     if (threadIdx.x == 0) out[blockIdx.x] = a / (float)n;
 }
-PDF_API int pdf_rowloss_fwd(const float* pred, const float* tgt, long rows, long n, int mode, float* out, hipStream_t s) {
+PDF_API int pdf_rowloss_fwd(const float* pred, const float* tgt, long rows, long n, int mode, float* out, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (rows <= 0 || n <= 0) return 0;
     hipLaunchKernelGGL(rowloss_fwd_kernel, dim3((unsigned)rows), dim3(256), 0, s, pred, tgt, n, mode, out);
     PDF_LAUNCH_CHECK();
@@ -54,7 +55,8 @@ __global__ void rowloss_bwd_kernel(const float* __restrict__ pred, const float* 
         dpred[i] = mode == 0 ? (d > 0.f ? g : (d < 0.f ? -g : 0.f)) : 2.f * d * g;
     }
 }
-PDF_API int pdf_rowloss_bwd(const float* pred, const float* tgt, const float* gout, long rows, long n, int mode, float* dpred, hipStream_t s) {
+PDF_API int pdf_rowloss_bwd(const float* pred, const float* tgt, const float* gout, long rows, long n, int mode, float* dpred, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (rows <= 0 || n <= 0) return 0;
     hipLaunchKernelGGL(rowloss_bwd_kernel, dim3(grid_for(rows * n)), dim3(256), 0, s, pred, tgt, gout, n, mode, dpred, rows * n);
     PDF_LAUNCH_CHECK();
@@ -98,7 +100,8 @@ __global__ __launch_bounds__(256) void face_loss_fwd_kernel(const float* __restr
     ae = block_sum_256(ae, sm);
     if (threadIdx.x == 0) { part[blockIdx.x * 2] = an; part[blockIdx.x * 2 + 1] = ae; }
 }
-PDF_API int pdf_face_loss_fwd(const float* pred, const float* gt, const long long* faces, int G, int B, int V, int Fc, float* part, hipStream_t s) {
+PDF_API int pdf_face_loss_fwd(const float* pred, const float* gt, const long long* faces, int G, int B, int V, int Fc, float* part, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (G * B <= 0) return 0;
     hipLaunchKernelGGL(face_loss_fwd_kernel, dim3(G * B), dim3(256), 0, s, pred, gt, faces, B, V, Fc, part);
     PDF_LAUNCH_CHECK();
@@ -156,7 +159,8 @@ __global__ __launch_bounds__(256) void face_loss_bwd_kernel(const float* __restr
     for (int i = threadIdx.x; i < V * 3; i += 256) o[i] = acc[i];
 }
 PDF_API int pdf_face_loss_bwd(const float* pred, const float* gt, const long long* faces, int G, int B, int V, int Fc,
-                              const float* wn, const float* we, float* dpred, hipStream_t s) {
+                              const float* wn, const float* we, float* dpred, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (V > FACE_MAXV) return PDF_E_BADARG;
     if (G * B <= 0) return 0;
     hipLaunchKernelGGL(face_loss_bwd_kernel, dim3(G * B), dim3(256), 0, s, pred, gt, faces, B, V, Fc, wn, we, dpred);
@@ -236,7 +240,8 @@ __global__ __launch_bounds__(64) void dense_loss_finalize_kernel(const DenseLoss
 PDF_API long pdf_dense_loss_workspace_floats(int B) { return 3L * B * 8 * 3; }
 PDF_API int pdf_dense_loss_fwd(const float* mask, const float* mask_gt, int mask_c, int mask_hw,
                                const float* hms, const float* hms_gt, int hms_c, int hms_hw,
-                               const float* hm, const float* hm_gt, int hm_c, int hm_hw, int B, float* ws, float* out, hipStream_t s) {
+                               const float* hm, const float* hm_gt, int hm_c, int hm_hw, int B, float* ws, float* out, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     DenseLoss a = {{{mask, mask_gt, nullptr, mask_c, mask_hw}, {hms, hms_gt, nullptr, hms_c, hms_hw}, {hm, hm_gt, nullptr, hm_c, hm_hw}}, B, 8};
     hipLaunchKernelGGL(dense_loss_partial_kernel, dim3(a.nblk, B, 3), dim3(256), 0, s, a, ws);
@@ -282,7 +287,8 @@ __global__ __launch_bounds__(256) void dense_loss_bwd_kernel(const DenseLoss a, 
 PDF_API int pdf_dense_loss_bwd(const float* mask, const float* mask_gt, float* dmask, int mask_c, int mask_hw,
                                const float* hms, const float* hms_gt, float* dhms, int hms_c, int hms_hw,
                                const float* hm, const float* hm_gt, float* dhm, int hm_c, int hm_hw, int B,
-                               const float* g_mask, const float* g_hms, const float* g_hm, const float* stat, hipStream_t s) {
+                               const float* g_mask, const float* g_hms, const float* g_hm, const float* stat, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     DenseLoss a = {{{mask, mask_gt, g_mask ? dmask : nullptr, mask_c, mask_hw}, {hms, hms_gt, g_hms ? dhms : nullptr, hms_c, hms_hw},
                     {hm, hm_gt, g_hm ? dhm : nullptr, hm_c, hm_hw}}, B, 8};
@@ -307,7 +313,8 @@ __global__ __launch_bounds__(256) void point_dist_sum_kernel(const float* __rest
     a = block_sum_256(a, sm);
     if (threadIdx.x == 0) out[blockIdx.x] = a;
 }
-PDF_API int pdf_point_dist_sum(const float* pred, const float* gt, int rows, int n, int dim, float* out, hipStream_t s) {
+PDF_API int pdf_point_dist_sum(const float* pred, const float* gt, int rows, int n, int dim, float* out, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (rows <= 0 || n <= 0) return 0;
     if (dim < 1 || dim > 4) return PDF_E_BADARG;
     hipLaunchKernelGGL(point_dist_sum_kernel, dim3(rows), dim3(256), 0, s, pred, gt, n, dim, out);
@@ -332,20 +339,6 @@ PDF_API int pdf_point_dist_sum(const float* pred, const float* gt, int rows, int
 #define ML_V 778
 #define ML_VG 252
 #define ML_J 21
-struct MeshLoss {
-    const float* vp; const float* v2p; const float* hd3; const float* hd2; const float* r;              // predictions [2][B][...]
-    const float* vgt[2]; const float* jgt[2]; const float* v2gt[2]; const float* lmsgt[2];              // ground truth per hand [B][...] (the batch's own tensors)
-    const long long* ind; const float* K; const float* valid;                                          // [B][2] i64, [B][3][3], [B][2]
-    const float* reg[2]; const long long* faces; const long long* perm[2];                              // [21][778] x 2, [2][F][3], [1008] x 2
-    int B, Fc, size, down;
-    float* part;                                                                                        // [2][B][MLP]
-    float* out;                                                                                         // forward: see mesh_loss_finalize_kernel
-    float coef[12];                                                                                     // weights of the reference's sum (:610-640), order of `out`
-    // backward
-    const float* gmp;                                                                                   // [B] upstream gradient of the weighted sum out[4 + 8 B ..]
-    int edge_grad;
-    float* dvp; float* dv2p; float* dhd3; float* dhd2; float* dr;
-};
 __constant__ int ml_bone_a[20] = {0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 0, 13, 14, 15, 0, 17, 18, 19};
 __constant__ int ml_bone_c[20] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20};
 
@@ -353,7 +346,7 @@ __constant__ int ml_bone_c[20] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14,
 struct MlShared {
     float jp[ML_J * 3], jg[ML_J * 3], lms[ML_J * 2], root_pred[3], root_gt[3], ax, ay, z;
 };
-__device__ __forceinline__ void ml_common(const MeshLoss& a, int g, int b, MlShared& S) {
+__device__ __forceinline__ void ml_common(const PdfMeshLoss& a, int g, int b, MlShared& S) {
     const long gb = (long)g * a.B + b;
     const float* vp = a.vp + gb * ML_V * 3;
     const float* vg = a.vgt[g] + (long)b * ML_V * 3;
@@ -398,7 +391,7 @@ __device__ __forceinline__ void ml_common(const MeshLoss& a, int g, int b, MlSha
 // ground truth of the GCN-level terms: node i of the 252 = mean of mean of GCN nodes 4i .. 4i + 3 (two pair-averagings, :117-122)
 __device__ __forceinline__ float ml_pool4(float x0, float x1, float x2, float x3) { return ((x0 + x1) * 0.5f + (x2 + x3) * 0.5f) * 0.5f; }
 
-__global__ __launch_bounds__(ML_T) void mesh_loss_fwd_kernel(const MeshLoss a) {
+__global__ __launch_bounds__(ML_T) void mesh_loss_fwd_kernel(const PdfMeshLoss a) {
     __shared__ MlShared S;
     __shared__ float sm[ML_T / 64];
     const int g = blockIdx.x / a.B, b = blockIdx.x - g * a.B;
@@ -481,7 +474,7 @@ __global__ __launch_bounds__(ML_T) void mesh_loss_fwd_kernel(const MeshLoss a) {
 // out layout (floats): [0] verts2d, [1] norm, [2] edge, [3] gcn_2d (scalars), then 8 vectors of B: root, verts, abs_verts, gcn, abs_joints,
 // joints2d, joints, bone  (the weights of `valid` and the x1000 of the absolute terms as in the reference, :506-525), then the weighted sum
 // sum_k coef[k] term_k per sample [B] (what CtdetLoss.total adds up for these twelve terms)
-__global__ __launch_bounds__(64) void mesh_loss_finalize_kernel(const MeshLoss a) {
+__global__ __launch_bounds__(64) void mesh_loss_finalize_kernel(const PdfMeshLoss a) {
     const int lane = threadIdx.x, B = a.B;
     const float k2 = (2.f / a.size) * (2.f / a.size);
     float t0 = 0.f, t3 = 0.f, t4 = 0.f, t6 = 0.f, m10[2] = {0.f, 0.f};
@@ -520,7 +513,8 @@ __global__ __launch_bounds__(64) void mesh_loss_finalize_kernel(const MeshLoss a
         a.out[4 + 8 * B + b] = t;
     }
 }
-PDF_API int pdf_mesh_loss_fwd(const MeshLoss* a, hipStream_t s) {
+PDF_API int pdf_mesh_loss_fwd(const PdfMeshLoss* a, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (a == nullptr || a->B < 1 || a->part == nullptr || a->out == nullptr || a->Fc < 1) return PDF_E_BADARG;
     hipLaunchKernelGGL(mesh_loss_fwd_kernel, dim3(2 * a->B), dim3(ML_T), 0, s, *a);
     hipLaunchKernelGGL(mesh_loss_finalize_kernel, dim3(1), dim3(64), 0, s, *a);
@@ -529,7 +523,7 @@ PDF_API int pdf_mesh_loss_fwd(const MeshLoss* a, hipStream_t s) {
 }
 
 // backward: gradients of sum_k gout[k] * out[k] with respect to vp, v2p, hd3, hd2, r
-__global__ __launch_bounds__(ML_T) void mesh_loss_bwd_kernel(const MeshLoss a) {
+__global__ __launch_bounds__(ML_T) void mesh_loss_bwd_kernel(const PdfMeshLoss a) {
     __shared__ MlShared S;
     __shared__ float acc[ML_V * 3];                                       // d vp of this (hand, sample)
     __shared__ float djp[ML_J * 3], dlms[ML_J * 2], droot[3], gsum[2];
@@ -702,10 +696,11 @@ __global__ __launch_bounds__(ML_T) void mesh_loss_bwd_kernel(const MeshLoss a) {
         d[2] = droot[1] * S.z / (100.f * (K[4] + 1e-7f));
     }
 }
-PDF_API int pdf_mesh_loss_bwd(const MeshLoss* a, hipStream_t s) {
+PDF_API int pdf_mesh_loss_bwd(const PdfMeshLoss* a, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (a == nullptr || a->B < 1 || a->gmp == nullptr || a->dvp == nullptr || a->dv2p == nullptr || a->dhd3 == nullptr || a->dhd2 == nullptr || a->dr == nullptr) return PDF_E_BADARG;
     hipLaunchKernelGGL(mesh_loss_bwd_kernel, dim3(2 * a->B), dim3(ML_T), 0, s, *a);
     PDF_LAUNCH_CHECK();
     return 0;
 }
-PDF_API int pdf_debug_mesh_loss_size() { return (int)sizeof(MeshLoss); }
+PDF_API int pdf_debug_mesh_loss_size() { return (int)sizeof(PdfMeshLoss); }

@@ -135,7 +135,8 @@ __global__ __launch_bounds__(256) void mano_lbs_kernel(
 
 PDF_API int pdf_mano_lbs_fwd(const float* root_aa, const float* pose_aa, const float* shape, const float* trans,
                              const float* v_template, const float* shapedirs, const float* posedirs, const float* J_reg,
-                             const float* weights, int B, int left_side, int center_idx, float* verts, float* joints, hipStream_t s) {
+                             const float* weights, int B, int left_side, int center_idx, float* verts, float* joints, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     hipLaunchKernelGGL(mano_lbs_kernel, dim3(B), dim3(256), 0, s, root_aa, pose_aa, shape, trans, v_template, shapedirs, posedirs,
                        J_reg, weights, left_side, center_idx, verts, joints);
@@ -364,7 +365,8 @@ __global__ __launch_bounds__(256) void mano_lbs_bwd_kernel(
 PDF_API int pdf_mano_lbs_bwd(const float* root_aa, const float* pose_aa, const float* shape,
                              const float* v_template, const float* shapedirs, const float* posedirs, const float* J_reg,
                              const float* weights, int B, int left_side, int center_idx, const float* dverts, const float* djoints,
-                             float* droot, float* dpose, float* dshape, float* dtrans, hipStream_t s) {
+                             float* droot, float* dpose, float* dshape, float* dtrans, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     if (droot == nullptr || dpose == nullptr) return PDF_E_BADARG;
     hipLaunchKernelGGL(mano_lbs_bwd_kernel, dim3(B), dim3(256), 0, s, root_aa, pose_aa, shape, v_template, shapedirs, posedirs, J_reg, weights,
@@ -412,14 +414,16 @@ __global__ void mano_split_coeff_kernel(const float* __restrict__ params, float*
     }
 }
 PDF_API int pdf_mano_split_coeff(const float* params, int ldp, long HW, const long* ind, const float* K, int B, int input_res, int down,
-                                 float* orient, float* pose, float* shape, float* trans, hipStream_t s) {
+                                 float* orient, float* pose, float* shape, float* trans, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     hipLaunchKernelGGL(mano_split_coeff_kernel, dim3(B, 2), dim3(64), 0, s, params, nullptr, ldp, HW, ind, K, B, input_res / down, down, orient, pose, shape, trans, 0);
     PDF_LAUNCH_CHECK();
     return 0;
 }
 PDF_API int pdf_mano_split_coeff_bwd(const float* params, float* dparams, int ldp, long HW, const long* ind, const float* K, int B, int input_res, int down,
-                                     const float* dorient, const float* dpose, const float* dtrans, hipStream_t s) {
+                                     const float* dorient, const float* dpose, const float* dtrans, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
     hipLaunchKernelGGL(mano_split_coeff_kernel, dim3(B, 2), dim3(64), 0, s, params, dparams, ldp, HW, ind, K, B, input_res / down, down,
                        const_cast<float*>(dorient), const_cast<float*>(dpose), nullptr, const_cast<float*>(dtrans), 1);
@@ -475,7 +479,8 @@ __global__ __launch_bounds__(256) void bmm_strided_wave_kernel(const float* __re
 
 PDF_API int pdf_bmm_strided(const float* A, const float* Bm, float* C, int batch, int M, int N, int K, int RB,
                             long sab, long sar, long sam, long sak, long sbb, long sbr, long sbk, long sbn,
-                            long scb, long scm, long scn, int beta, hipStream_t s) {
+                            long scb, long scm, long scn, int beta, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)batch * M * N;
     if (total <= 0) return 0;
     if ((long)K * RB >= 128 && total <= (1L << 16))

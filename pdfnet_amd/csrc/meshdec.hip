@@ -112,38 +112,7 @@ __device__ unsigned long long g_md_stamps[8 * 3 * 64];
 #define MD_STAMP(KID, N) do { } while (0)
 #endif
 
-// ---- argument block of one level (mirrors PdfMeshLevel of include/pdfnet_hip.h field for field) --------------------------------
-struct MdLin { const float* w[2]; const float* b[2]; };            // [hand]
-struct MdLN { const float* g[2]; const float* b[2]; };
-struct MdGcn { MdLin fc1, fc2, sc; MdLN n2, n3; unsigned long long seed; };
-struct MdAttn {
-    MdLN ln; MdLin q, k, v, fc; MdLN ffln; MdLin f1, f2;
-    unsigned long long seed_att, seed_z, seed_t, seed_x;
-};
-// gradient outputs (accumulated, += ): same shapes as the parameters
-struct MdLinG { float* w[2]; float* b[2]; };
-struct MdLNG { float* g[2]; float* b[2]; };
-struct MdGcnG { MdLinG fc1, fc2, sc; MdLNG n2, n3; };
-struct MdAttnG { MdLNG ln; MdLinG q, k, v, fc; MdLNG ffln; MdLinG f1, f2; };
-
-struct PdfMeshLevel {
-    int level, B, training, cin0;                 // level 0..2 (V = 63 << level, C = 256 >> level); cin0 = width of x (= 2 C)
-    float p;                                      // dropout probability (0 in eval mode)
-    const unsigned long long* step;               // device step counter mixed into every dropout seed (hipGraph replays draw fresh masks)
-    const float* x;                               // [2][B][V][cin0] level input (position embedding already added)
-    float* out;                                   // [2][B][V][C] level output
-    const int* ell_col[2]; const float* ell_val[2]; const int* ell_colT[2]; const float* ell_valT[2]; int ell_w;
-    MdGcn gcn[4];
-    MdAttn self_, cross;
-    float* tape;                                  // training: pdf_mesh_tape_floats(level, B) floats (forward writes, backward reads)
-    float* qkv;                                   // [3][2][B][V][C] cross-hand q / k / v (part 1 -> part 2; also part of the tape)
-    // backward
-    const float* dout;                            // [2][B][V][C]
-    float* dx;                                    // [2][B][V][cin0]
-    float* gtape;                                 // pdf_mesh_gtape_floats(level, B) floats: the dY operands of the weight-gradient GEMMs
-    MdGcnG ggcn[4]; MdAttnG gself, gcross;
-    float* wg_ws; long wg_ws_floats;              // workspace of the weight-gradient launches
-};
+// The argument block of one level is PdfMeshLevel of pdfnet_hip.h (parameters PdfMeshLin / LN / Gcn / Attn, their gradients PdfMesh*G).
 
 template <int LV> struct Cfg {
     static constexpr int V = 63 << LV, VP = 64 << LV, C = 256 >> LV, LD = C + 4, DH = C / 4, H = 4;
@@ -754,7 +723,7 @@ __device__ __forceinline__ void acc_to_lds(f32x16 (&acc)[Cfg<LV>::WMT][Cfg<LV>::
 // One GCN_ResBlock (gcn.py:99-110).  In: x in HBM ([V][cin] rows of this (hand, sample)); when `x_in_lds` the block input (cin == C) already
 // sits in XA.  Out: the block output in XA (and in HBM: `xout`).
 template <int LV>
-__device__ __forceinline__ void gcn_block(Ctx<LV>& c, const PdfMeshLevel& a, const MdGcn& P, int blk, const float* __restrict__ x, int cin, bool x_in_lds,
+__device__ __forceinline__ void gcn_block(Ctx<LV>& c, const PdfMeshLevel& a, const PdfMeshGcn& P, int blk, const float* __restrict__ x, int cin, bool x_in_lds,
                                           const TapeOff& to, float* __restrict__ xout, bool relu_out) {
     using G = Cfg<LV>;
     constexpr int C = G::C;
@@ -822,7 +791,7 @@ __device__ __forceinline__ void gcn_block(Ctx<LV>& c, const PdfMeshLevel& a, con
 
 // LN -> q / k / v projections.  In: x in XA.  Out: h (tape), q / k / v in HBM.  XA keeps h.
 template <int LV>
-__device__ __forceinline__ void qkv_stage(Ctx<LV>& c, const MdAttn& P, float* __restrict__ hsave, float* __restrict__ stsave,
+__device__ __forceinline__ void qkv_stage(Ctx<LV>& c, const PdfMeshAttn& P, float* __restrict__ hsave, float* __restrict__ stsave,
                                           float* __restrict__ q, float* __restrict__ k, float* __restrict__ v) {
     using G = Cfg<LV>;
     constexpr int C = G::C;
@@ -830,7 +799,7 @@ __device__ __forceinline__ void qkv_stage(Ctx<LV>& c, const MdAttn& P, float* __
     __syncthreads();
     ln_rows<LV>(c.XA, P.ln.g[hd], P.ln.b[hd], 1e-6f, false, nullptr, stsave, hsave);
     __syncthreads();
-    const MdLin* lin[3] = {&P.q, &P.k, &P.v};
+    const PdfMeshLin* lin[3] = {&P.q, &P.k, &P.v};
     float* dst[3] = {q, k, v};
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
@@ -846,7 +815,7 @@ __device__ __forceinline__ void qkv_stage(Ctx<LV>& c, const MdAttn& P, float* __
 // attention (keys / values of stacked sample bkv) -> fc -> z = x + dropout(o) -> LN -> fc1 + ReLU + dropout -> fc2 -> x + dropout: the level's
 // second half of SelfAttn.forward / inter_attn.forward (self_attn.py:63-85, 24-33; inter_attn.py:82-125)
 template <int LV>
-__device__ __forceinline__ void attn_tail_stage(Ctx<LV>& c, const MdAttn& P, const float* __restrict__ xres /* HBM [V][C]: the residual stream */,
+__device__ __forceinline__ void attn_tail_stage(Ctx<LV>& c, const PdfMeshAttn& P, const float* __restrict__ xres /* HBM [V][C]: the residual stream */,
                                                 const float* __restrict__ q, const float* __restrict__ kk, const float* __restrict__ vv, int bkv,
                                                 float* __restrict__ asave, float* __restrict__ statsave, float* __restrict__ zsave, float* __restrict__ stzsave,
                                                 float* __restrict__ hnsave, float* __restrict__ tsave, float* __restrict__ xout) {
@@ -984,7 +953,7 @@ __global__ __launch_bounds__(MD_THREADS, 1) void mesh_att_kernel(const PdfMeshLe
     float* tape = a.tape;
     const long R = 2L * a.B * G::V;
     constexpr int A = CROSS ? 1 : 0;
-    const MdAttn& P = CROSS ? a.cross : a.self_;
+    const PdfMeshAttn& P = CROSS ? a.cross : a.self_;
     const float* xres = CROSS ? tape + to.xo(0) + c.row0 * C : tape + to.out(3) + c.row0 * C;
     const float* q = CROSS ? a.qkv : tape + to.q(0);
     const float* k = CROSS ? a.qkv + R * C : tape + to.k(0);
@@ -1035,12 +1004,13 @@ static int mesh_check(const PdfMeshLevel* a) {
 #define pdf_mesh_level_fwd pdf_mesh_level_fwd_bf16
 #define pdf_mesh_level_bwd pdf_mesh_level_bwd_bf16
 #endif
-PDF_API int pdf_mesh_level_fwd(const PdfMeshLevel* a, hipStream_t stream) {
+PDF_API int pdf_mesh_level_fwd(const PdfMeshLevel* a, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (int rc = mesh_check(a)) return rc;
     switch (a->level) {
-        case 0: return mesh_fwd_launch<0>(*a, stream);
-        case 1: return mesh_fwd_launch<1>(*a, stream);
-        default: return mesh_fwd_launch<2>(*a, stream);
+        case 0: return mesh_fwd_launch<0>(*a, s);
+        case 1: return mesh_fwd_launch<1>(*a, s);
+        default: return mesh_fwd_launch<2>(*a, s);
     }
 }
 #if !MD_BF16
@@ -1363,8 +1333,8 @@ __global__ __launch_bounds__(MD_THREADS, 1) void mesh_att_bwd1_kernel(const PdfM
     const int hd = c.hand;
     const TapeOff to = tape_offsets(LV, a.B);
     const GTapeOff go = gtape_offsets(LV, a.B);
-    const MdAttn& P = CROSS ? a.cross : a.self_;
-    const MdAttnG& GP = CROSS ? a.gcross : a.gself;
+    const PdfMeshAttn& P = CROSS ? a.cross : a.self_;
+    const PdfMeshAttnG& GP = CROSS ? a.gcross : a.gself;
     const float* tape = a.tape;
     float* gt = a.gtape;
     const long ro = c.row0 * C;
@@ -1439,8 +1409,8 @@ __global__ __launch_bounds__(MD_THREADS, 1) void mesh_att_bwd2_kernel(const PdfM
     const int hd = c.hand;
     const TapeOff to = tape_offsets(LV, a.B);
     const GTapeOff go = gtape_offsets(LV, a.B);
-    const MdAttn& P = CROSS ? a.cross : a.self_;
-    const MdAttnG& GP = CROSS ? a.gcross : a.gself;
+    const PdfMeshAttn& P = CROSS ? a.cross : a.self_;
+    const PdfMeshAttnG& GP = CROSS ? a.gcross : a.gself;
     const float* tape = a.tape;
     float* gt = a.gtape;
     const long R = 2L * a.B * G::V, VC = (long)G::V * C, ro = c.row0 * C;
@@ -1522,8 +1492,8 @@ __device__ __forceinline__ void gcn_bwd_head(Ctx<LV>& c, const PdfMeshLevel& a, 
     using G = Cfg<LV>;
     constexpr int C = G::C;
     const int hd = c.hand;
-    const MdGcn& P = a.gcn[blk];
-    const MdGcnG& GP = a.ggcn[blk];
+    const PdfMeshGcn& P = a.gcn[blk];
+    const PdfMeshGcnG& GP = a.ggcn[blk];
     const float* tape = a.tape;
     float* gt = a.gtape;
     const long ro = c.row0 * C;
@@ -1585,7 +1555,7 @@ __global__ __launch_bounds__(MD_THREADS, 1) void mesh_gcn_bwd_kernel(const PdfMe
     load_rows<LV>(XA, gt + (blk == 3 ? go.att(0, 8) : go.dz(blk)) + ro, C, 0);
     __syncthreads();
     gcn_bwd_head<LV>(c, a, blk, to, go);
-    const MdGcn& P = a.gcn[blk];
+    const PdfMeshGcn& P = a.gcn[blk];
     if constexpr (!BLK0) {
         // fc1 + shortcut backward: d x = dy W1[even] + dz Ws + L^T (dy W1[odd])
         f32x16 acc[G::WMT][G::WNT];
@@ -1635,13 +1605,6 @@ __global__ __launch_bounds__(MD_THREADS, 1) void mesh_gcn_bwd_kernel(const PdfMe
         MD_STAMP(4, 6);                                                 // block 0: fc1 + shortcut backward
     }
 }
-
-// the library's own weight-gradient GEMMs (gemm.hip) and stream wait (elementwise.hip)
-extern "C" int pdf_linear_bwd_weight(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy,
-                                     int accumulate, hipStream_t s);
-extern "C" int pdf_linear_bwd_weight_pair(const float* x, const float* dy, float* dw0, float* dw1, float* db0, float* db1, float* ws, long ws_floats, int M, int N,
-                                          int K, int ldx, int lddy, int accumulate, hipStream_t s);
-extern "C" int pdf_stream_wait(hipStream_t waiter, hipStream_t signaler);
 
 template <int LV>
 static int mesh_bwd_launch(const PdfMeshLevel& a, hipStream_t s, hipStream_t side) {
@@ -1711,7 +1674,7 @@ static int mesh_bwd_launch(const PdfMeshLevel& a, hipStream_t s, hipStream_t sid
         MD_WG_PAIR(xi, cin, gt + go.dz(i), a.ggcn[i].sc, cin)
     }
     for (int A = 0; A < 2; ++A) {
-        const MdAttnG& GP = A ? a.gcross : a.gself;
+        const PdfMeshAttnG& GP = A ? a.gcross : a.gself;
         const float* hn = tape + to.h(A);
         if (A == 0) {
             MD_WG_PAIR(hn, C, gt + go.att(A, 3), GP.q, C)
@@ -1720,7 +1683,7 @@ static int mesh_bwd_launch(const PdfMeshLevel& a, hipStream_t s, hipStream_t sid
             MD_WG_PAIR(tape + to.a_(A), C, gt + go.att(A, 2), GP.fc, C)
         } else {
             // the cross-hand projections are shared by both hands (inter_attn.py:82-108): one product over all 2 M rows
-            const MdLinG* gl[4] = {&GP.q, &GP.k, &GP.v, &GP.fc};
+            const PdfMeshLinG* gl[4] = {&GP.q, &GP.k, &GP.v, &GP.fc};
             const float* xs[4] = {hn, hn, hn, tape + to.a_(A)};
             const int slot[4] = {3, 4, 5, 2};
             for (int t = 0; t < 4; ++t)
@@ -1736,13 +1699,14 @@ static int mesh_bwd_launch(const PdfMeshLevel& a, hipStream_t s, hipStream_t sid
 
 // One DualGraphLayer backward: five launches on `stream`, then the layer's 28 weight-gradient GEMMs on `side_stream` (which first waits for `stream`).
 // Every parameter gradient is ACCUMULATED into its g* pointer (NULL weight pointer: that Linear's gradient is skipped).
-PDF_API int pdf_mesh_level_bwd(const PdfMeshLevel* a, hipStream_t stream, hipStream_t side_stream) {
+PDF_API int pdf_mesh_level_bwd(const PdfMeshLevel* a, void* stream, void* side_stream) {
+    hipStream_t s = (hipStream_t)stream, side = (hipStream_t)side_stream;
     if (int rc = mesh_check(a)) return rc;
     if (a->dout == nullptr || a->dx == nullptr || a->gtape == nullptr || a->wg_ws == nullptr || !a->training) return PDF_E_BADARG;
     switch (a->level) {
-        case 0: return mesh_bwd_launch<0>(*a, stream, side_stream);
-        case 1: return mesh_bwd_launch<1>(*a, stream, side_stream);
-        default: return mesh_bwd_launch<2>(*a, stream, side_stream);
+        case 0: return mesh_bwd_launch<0>(*a, s, side);
+        case 1: return mesh_bwd_launch<1>(*a, s, side);
+        default: return mesh_bwd_launch<2>(*a, s, side);
     }
 }
 

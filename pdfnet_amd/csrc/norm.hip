@@ -538,16 +538,17 @@ static int pdf_bn_train_fwd_impl(const float* x, int ldx, int C, long R, const f
 PDF_API int pdf_bn_train_fwd_x(const float* x, int ldx, int C, long R, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, float momentum, float eps,
                              const float* res, int ldr, int relu, float* y, int ldy,
-                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_train_fwd_impl(x, ldx, C, R, gamma, beta, running_mean, running_var, momentum, eps, res, ldr, relu, y, ldy, save_mean, save_rstd, scale, shift, ws, s, co); }
+                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_train_fwd_impl(x, ldx, C, R, gamma, beta, running_mean, running_var, momentum, eps, res, ldr, relu, y, ldy, save_mean, save_rstd, scale, shift, ws, s, co); }
 PDF_API int pdf_bn_train_fwd(const float* x, int ldx, int C, long R, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, float momentum, float eps,
                              const float* res, int ldr, int relu, float* y, int ldy,
-                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_train_fwd_impl(x, ldx, C, R, gamma, beta, running_mean, running_var, momentum, eps, res, ldr, relu, y, ldy, save_mean, save_rstd, scale, shift, ws, s, co); pdf_tls_publish(co); return rc; }
+                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_train_fwd_impl(x, ldx, C, R, gamma, beta, running_mean, running_var, momentum, eps, res, ldr, relu, y, ldy, save_mean, save_rstd, scale, shift, ws, s, co); pdf_tls_publish(co); return rc; }
 
 
 PDF_API int pdf_bn_eval_fwd(const float* x, int ldx, int C, long R, const float* gamma, const float* beta,
                             const float* running_mean, const float* running_var, float eps,
-                            const float* res, int ldr, int relu, float* y, int ldy, float* scale, float* shift, hipStream_t s) {
+                            const float* res, int ldr, int relu, float* y, int ldy, float* scale, float* shift, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R <= 0 || C <= 0) return 0;
     hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3(cdiv(C, 128)), dim3(128), 0, s, C, gamma, beta, running_mean, running_var, eps, scale, shift);
     PDF_LAUNCH_CHECK();
@@ -674,12 +675,12 @@ PDF_API int pdf_bn_train_bwd_x(const float* dy, int lddy, const float* y, int ld
                              const float* save_mean, const float* save_rstd, const float* gamma,
                              const float* scale, const float* shift, int C, long R,
                              float* dx, int lddx, float* dres, int lddr, float* dgamma, float* dbeta, int accumulate,
-                             float* ws, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_train_bwd_impl(dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, gamma, scale, shift, C, R, dx, lddx, dres, lddr, dgamma, dbeta, accumulate, ws, s, co); }
+                             float* ws, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_train_bwd_impl(dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, gamma, scale, shift, C, R, dx, lddx, dres, lddr, dgamma, dbeta, accumulate, ws, s, co); }
 PDF_API int pdf_bn_train_bwd(const float* dy, int lddy, const float* y, int ldy, int relu, const float* x, int ldx,
                              const float* save_mean, const float* save_rstd, const float* gamma,
                              const float* scale, const float* shift, int C, long R,
                              float* dx, int lddx, float* dres, int lddr, float* dgamma, float* dbeta, int accumulate,
-                             float* ws, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_train_bwd_impl(dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, gamma, scale, shift, C, R, dx, lddx, dres, lddr, dgamma, dbeta, accumulate, ws, s, co); pdf_tls_publish(co); return rc; }
+                             float* ws, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_train_bwd_impl(dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, gamma, scale, shift, C, R, dx, lddx, dres, lddr, dgamma, dbeta, accumulate, ws, s, co); pdf_tls_publish(co); return rc; }
 
 
 // ---------------------------------------------------------------------------------------------
@@ -813,16 +814,17 @@ static int pdf_bn_relu_maxk_fwd_impl(const float* y, int ldy, int C, long R, int
 PDF_API int pdf_bn_relu_maxk_fwd_x(const float* y, int ldy, int C, long R, int K, const float* gamma, const float* beta,
                                  float* running_mean, float* running_var, float momentum, float eps, int training,
                                  float* out, int ldo, int* arg, float* save_mean, float* save_rstd, float* scale, float* shift,
-                                 float* ws, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_relu_maxk_fwd_impl(y, ldy, C, R, K, gamma, beta, running_mean, running_var, momentum, eps, training, out, ldo, arg, save_mean, save_rstd, scale, shift, ws, s, co); }
+                                 float* ws, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_relu_maxk_fwd_impl(y, ldy, C, R, K, gamma, beta, running_mean, running_var, momentum, eps, training, out, ldo, arg, save_mean, save_rstd, scale, shift, ws, s, co); }
 PDF_API int pdf_bn_relu_maxk_fwd(const float* y, int ldy, int C, long R, int K, const float* gamma, const float* beta,
                                  float* running_mean, float* running_var, float momentum, float eps, int training,
                                  float* out, int ldo, int* arg, float* save_mean, float* save_rstd, float* scale, float* shift,
-                                 float* ws, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_relu_maxk_fwd_impl(y, ldy, C, R, K, gamma, beta, running_mean, running_var, momentum, eps, training, out, ldo, arg, save_mean, save_rstd, scale, shift, ws, s, co); pdf_tls_publish(co); return rc; }
+                                 float* ws, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_relu_maxk_fwd_impl(y, ldy, C, R, K, gamma, beta, running_mean, running_var, momentum, eps, training, out, ldo, arg, save_mean, save_rstd, scale, shift, ws, s, co); pdf_tls_publish(co); return rc; }
 
 // ws: pdf_bn_workspace_floats(C, R) + 3*C floats
 PDF_API int pdf_bn_relu_maxk_bwd(const float* dout, int lddo, const int* arg, const float* y, int ldy, const float* save_mean, const float* save_rstd,
                                  const float* gamma, const float* scale, const float* shift, int C, long R, int K,
-                                 float* dy, int lddy, float* dgamma, float* dbeta, int accumulate, float* ws, hipStream_t s) {
+                                 float* dy, int lddy, float* dgamma, float* dbeta, int accumulate, float* ws, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R <= 0 || C <= 0 || K <= 0) return 0;
     if (!v4_ok(C, {ldy, lddo, lddy}, {y, dout, dy, arg, save_mean, save_rstd, scale, shift, ws})) return PDF_E_BADARG;
     long chunks = bn_chunks(C, R);
@@ -889,11 +891,13 @@ int pdf_internal_colsum(const float* g, int ldg, int C, long R, float* out, int 
     return colsum_launch(g, ldg, C, R, out, nullptr, accumulate, ws, s);
 }
 long pdf_internal_colsum_ws(int C, long R) { return pdf_bn_workspace_floats(C, R); }
-PDF_API int pdf_colsum(const float* g, int ldg, int C, long R, float* out, int accumulate, float* ws, hipStream_t s) {
+PDF_API int pdf_colsum(const float* g, int ldg, int C, long R, float* out, int accumulate, float* ws, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return colsum_launch(g, ldg, C, R, out, nullptr, accumulate, ws, s);
 }
 // paired bias gradients: rows [0, R) -> out0, rows [R, 2R) -> out1; ws >= 2 * pdf_bn_workspace_floats(C, R)
-PDF_API int pdf_colsum_pair(const float* g, int ldg, int C, long R, float* out0, float* out1, int accumulate, float* ws, hipStream_t s) {
+PDF_API int pdf_colsum_pair(const float* g, int ldg, int C, long R, float* out0, float* out1, int accumulate, float* ws, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return colsum_launch(g, ldg, C, R, out0, out1, accumulate, ws, s);
 }
 
@@ -972,14 +976,16 @@ static int ln_fwd_launch(const float* x, int ldx, const float* add, int ldadd, f
     return 0;
 }
 PDF_API int pdf_layernorm_fwd(const float* x, int ldx, int F, long R, const float* gamma, const float* beta, float eps,
-                              float* y, int ldy, float* mean, float* rstd, hipStream_t s) {
+                              float* y, int ldy, float* mean, float* rstd, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return ln_fwd_launch(x, ldx, nullptr, 0, 0.f, 0, nullptr, F, R, R, gamma, beta, gamma, beta, eps, 0, nullptr, 0, y, ldy, mean, rstd, s);
 }
 // fused / paired form, see the kernel comment.  add == NULL: plain LayerNorm input (z unused).  R_split >= R: one parameter set.
 PDF_API int pdf_layernorm_fused_fwd(const float* x, int ldx, const float* add, int ldadd, float p, unsigned long long seed,
                                     const unsigned long long* step, int F, long R, long R_split,
                                     const float* gamma0, const float* beta0, const float* gamma1, const float* beta1, float eps, int act,
-                                    float* z, int ldz, float* y, int ldy, float* mean, float* rstd, hipStream_t s) {
+                                    float* z, int ldz, float* y, int ldy, float* mean, float* rstd, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return ln_fwd_launch(x, ldx, add, ldadd, p, seed, step, F, R, R_split, gamma0, beta0, gamma1, beta1, eps, act, z, ldz, y, ldy, mean, rstd, s);
 }
 
@@ -1086,7 +1092,8 @@ static int ln_bwd_launch(const float* dy, int lddy, const float* y, int ldy, int
     return 0;
 }
 PDF_API int pdf_layernorm_bwd(const float* dy, int lddy, const float* x, int ldx, int F, long R, const float* gamma,
-                              const float* mean, const float* rstd, float* dx, int lddx, float* dgamma, float* dbeta, hipStream_t s) {
+                              const float* mean, const float* rstd, float* dx, int lddx, float* dgamma, float* dbeta, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return ln_bwd_launch(dy, lddy, nullptr, 0, 0, x, ldx, F, R, R, gamma, gamma, mean, rstd, nullptr, 0, dx, lddx, nullptr, 0, 0.f, 0, nullptr,
                          dgamma, dbeta, dgamma, dbeta, s);
 }
@@ -1094,7 +1101,8 @@ PDF_API int pdf_layernorm_fused_bwd(const float* dy, int lddy, const float* y, i
                                     const float* gamma0, const float* gamma1, const float* mean, const float* rstd,
                                     const float* dz_in, int lddzin, float* dz, int lddz, float* dadd, int lddadd,
                                     float p, unsigned long long seed, const unsigned long long* step,
-                                    float* dgamma0, float* dbeta0, float* dgamma1, float* dbeta1, hipStream_t s) {
+                                    float* dgamma0, float* dbeta0, float* dgamma1, float* dbeta1, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     return ln_bwd_launch(dy, lddy, y, ldy, act, z, ldz, F, R, R_split, gamma0, gamma1, mean, rstd, dz_in, lddzin, dz, lddz, dadd, lddadd, p, seed, step,
                          dgamma0, dbeta0, dgamma1, dbeta1, s);
 }
@@ -1115,7 +1123,8 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* __restrict
     }
 }
 
-PDF_API int pdf_l2norm_fwd(const float* x, int ldx, int C, long R, const float* w, float eps, float* y, int ldy, float* norm, hipStream_t s) {
+PDF_API int pdf_l2norm_fwd(const float* x, int ldx, int C, long R, const float* w, float eps, float* y, int ldy, float* norm, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R <= 0) return 0;
     hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(grid_for(R * 64)), dim3(256), 0, s, x, ldx, C, R, w, eps, y, ldy, norm);
     PDF_LAUNCH_CHECK();
@@ -1165,7 +1174,8 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 }
 
 PDF_API int pdf_l2norm_bwd(const float* dy, int lddy, const float* x, int ldx, int C, long R, const float* w, float eps,
-                           const float* norm, float* dx, int lddx, float* dw, hipStream_t s) {
+                           const float* norm, float* dx, int lddx, float* dw, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R <= 0) return 0;
     if (C > 64 * L2_MAXV) return PDF_E_BADARG;
     int grid = grid_for(R * 64, 256, 1024);
@@ -1320,13 +1330,14 @@ static int pdf_l2norm_cat_fwd_impl(int nparts, const float* const* x, const int*
     return 0;
 }
 PDF_API int pdf_l2norm_cat_fwd_x(int nparts, const float* const* x, const int* C, const float* const* w, float eps, long R,
-                               float* y, int ldy, float* const* norm, hipStream_t s, PdfCallOpts* opts) { PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_l2norm_cat_fwd_impl(nparts, x, C, w, eps, R, y, ldy, norm, s, co); }
+                               float* y, int ldy, float* const* norm, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_l2norm_cat_fwd_impl(nparts, x, C, w, eps, R, y, ldy, norm, s, co); }
 PDF_API int pdf_l2norm_cat_fwd(int nparts, const float* const* x, const int* C, const float* const* w, float eps, long R,
-                               float* y, int ldy, float* const* norm, hipStream_t s) { PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_l2norm_cat_fwd_impl(nparts, x, C, w, eps, R, y, ldy, norm, s, co); pdf_tls_publish(co); return rc; }
+                               float* y, int ldy, float* const* norm, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_l2norm_cat_fwd_impl(nparts, x, C, w, eps, R, y, ldy, norm, s, co); pdf_tls_publish(co); return rc; }
 
 // dw[i] must be zero-filled (atomically accumulated)
 PDF_API int pdf_l2norm_cat_bwd(int nparts, const float* dy, int lddy, const float* const* x, const int* C, const float* const* w, float eps, long R,
-                               float* const* norm, float* const* dx, float* const* dw, void* const* dx16, hipStream_t s) {
+                               float* const* norm, float* const* dx, float* const* dw, void* const* dx16, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (R <= 0) return 0;
     L2Parts p = {};
     if (int rc = l2_parts(p, nparts, x, w, norm, dx, dw, C)) return rc;

@@ -117,7 +117,8 @@ __global__ __launch_bounds__(256) void knn_ball_group_kernel(
 }
 
 PDF_API int pdf_knn_ball_group(const float* pts, int ldp, int C, int Bc, int N, int S, int K, float r2,
-                               int* idx, float* grouped, int ldg, hipStream_t s) {
+                               int* idx, float* grouped, int ldg, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (N < 1 || N > 1024 || K > N || K < 1 || S > N || C < 3 || ldp < C || (grouped && ldg < C)) return PDF_E_BADARG;
     dim3 grid(cdiv(S, 16), Bc);
     size_t smem = (size_t)3 * N * sizeof(float) + (size_t)4 * K * sizeof(int);
@@ -159,7 +160,8 @@ __global__ __launch_bounds__(256) void group_bwd_kernel(const float* __restrict_
 }
 
 PDF_API int pdf_group_bwd(const float* dg, int ldg, const int* idx, float* dpts, int ldd, int C,
-                          int Bc, int N, int S, int K, hipStream_t s) {
+                          int Bc, int N, int S, int K, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long rows = (long)Bc * S;
     hipLaunchKernelGGL(group_bwd_kernel, dim3(grid_for(rows * 64)), dim3(256), 0, s, dg, ldg, idx, dpts, ldd, C, N, S, K, rows);
     PDF_LAUNCH_CHECK();
@@ -187,7 +189,8 @@ __global__ __launch_bounds__(256) void gather_sub_fwd_kernel(const float* __rest
     }
 }
 PDF_API int pdf_gather_sub_fwd(const float* u, int ldu, const float* v, int ldv, const int* idx, int Bc, int N, int S, int K, int C,
-                               float* y, int ldy, hipStream_t s) {
+                               float* y, int ldy, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (C % 4 != 0 || ldu % 4 != 0 || ldv % 4 != 0 || ldy % 4 != 0) return PDF_E_BADARG;
     const long total = (long)Bc * S * K * (C / 4);
     if (total == 0) return 0;
@@ -314,7 +317,8 @@ __global__ __launch_bounds__(INV_NT) void invert_index_kernel(const int* __restr
     }
     for (int eb = e0 + INV_KR * 64; eb < e1; eb += 64) place(key_of(0, eb + lane), eb + lane);
 }
-PDF_API int pdf_invert_index(const int* idx, int Bc, int N, int E, int* start, int* list, int* tmp, hipStream_t s) {
+PDF_API int pdf_invert_index(const int* idx, int Bc, int N, int E, int* start, int* list, int* tmp, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     (void)tmp;
     if (Bc <= 0 || E <= 0) return 0;
     if (N <= 0) return PDF_E_BADARG;
@@ -390,7 +394,8 @@ __global__ __launch_bounds__(256) void gather_sub_bwd_dv_kernel(const float* __r
     }
 }
 PDF_API int pdf_gather_sub_bwd_sorted(const float* dy, int lddy, const int* start, const int* list, float* du, int ldu, float* dv, int ldv,
-                                      int Bc, int N, int S, int K, int C, hipStream_t s) {
+                                      int Bc, int N, int S, int K, int C, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (C > 256 || C % 4 != 0 || lddy % 4 != 0 || ldu % 4 != 0 || ldv % 4 != 0) return PDF_E_BADARG;
     const long pts = (long)Bc * N, rows = (long)Bc * S;
     if (pts == 0 || rows == 0) return 0;
@@ -409,7 +414,8 @@ PDF_API int pdf_gather_sub_bwd_sorted(const float* dy, int lddy, const int* star
 }
 
 PDF_API int pdf_gather_sub_bwd(const float* dy, int lddy, const int* idx, float* du, int ldu, float* dv, int ldv,
-                               int Bc, int N, int S, int K, int C, hipStream_t s) {
+                               int Bc, int N, int S, int K, int C, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (C > 256) return PDF_E_BADARG;
     const long rows = (long)Bc * S;
     if (rows == 0) return 0;
@@ -443,7 +449,8 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
 }
 
 PDF_API int pdf_gather_rows(const float* feat, int ldf, int C, long HW, const long* ind, long ind_bstride,
-                            int B, int M, int R, int shift, float* out, int ldo, hipStream_t s) {
+                            int B, int M, int R, int shift, float* out, int ldo, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)B * M;
     if (total == 0) return 0;
     hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(total * 64)), dim3(256), 0, s, feat, ldf, C, HW, ind, ind_bstride, M, R, shift, out, ldo, total);
@@ -472,7 +479,8 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restri
 }
 
 PDF_API int pdf_scatter_rows_add(const float* dout, int ldo, int C, long HW, const long* ind, long ind_bstride,
-                                 int B, int M, int R, int shift, float* dfeat, int ldf, hipStream_t s) {
+                                 int B, int M, int R, int shift, float* dfeat, int ldf, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)B * M;
     if (total == 0) return 0;
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(total * 64)), dim3(256), 0, s, dout, ldo, C, HW, ind, ind_bstride, M, R, shift, dfeat, ldf, total);
@@ -499,7 +507,8 @@ __global__ __launch_bounds__(256) void maxk_fwd_kernel(const float* __restrict__
     }
 }
 
-PDF_API int pdf_maxk_fwd(const float* x, int ldx, int C, long R, int K, float* y, int ldy, int* arg, hipStream_t s) {
+PDF_API int pdf_maxk_fwd(const float* x, int ldx, int C, long R, int K, float* y, int ldy, int* arg, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = R * C;
     if (total == 0) return 0;
     hipLaunchKernelGGL(maxk_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, ldx, C, K, y, ldy, arg, total);
@@ -519,7 +528,8 @@ __global__ __launch_bounds__(256) void maxk_bwd_kernel(const float* __restrict__
     }
 }
 
-PDF_API int pdf_maxk_bwd(const float* dy, int ldy, const int* arg, int C, long R, int K, float* dx, int ldx, hipStream_t s) {
+PDF_API int pdf_maxk_bwd(const float* dy, int ldy, const int* arg, int C, long R, int K, float* dx, int ldx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = R * K * C;
     if (total == 0) return 0;
     hipLaunchKernelGGL(maxk_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, s, dy, ldy, arg, C, K, dx, ldx, total);
@@ -562,7 +572,8 @@ __global__ __launch_bounds__(256) void window_kernel(float* __restrict__ feat, i
 }
 
 PDF_API int pdf_window_op(float* feat, int ldf, int C, int H, int W, const long* ind, long ind_bstride,
-                          int B, int M, int r, float* buf, const float* src, int mode, hipStream_t s) {
+                          int B, int M, int r, float* buf, const float* src, int mode, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     long total = (long)B * M * (2 * r + 1) * (2 * r + 1);
     if (total <= 0) return 0;
     hipLaunchKernelGGL(window_kernel, dim3(grid_for(total * 64)), dim3(256), 0, s, feat, ldf, C, H, W, ind, ind_bstride, M, r, buf, src, mode, total);
@@ -608,7 +619,8 @@ __global__ __launch_bounds__(256) void nms_top1_kernel(const float* __restrict__
     if (threadIdx.x == 0) { ind[blockIdx.x] = si[0]; if (score) score[blockIdx.x] = sv[0]; }
 }
 
-PDF_API int pdf_nms_top1(const float* hm, int BC, int H, int W, long* ind, float* score, hipStream_t s) {
+PDF_API int pdf_nms_top1(const float* hm, int BC, int H, int W, long* ind, float* score, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (BC <= 0) return 0;
     hipLaunchKernelGGL(nms_top1_kernel, dim3(BC), dim3(256), 0, s, hm, H, W, ind, score);
     PDF_LAUNCH_CHECK();
@@ -744,7 +756,8 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(const float* __restrict__ 
         cur = (int)(0xffffffffu - wlo);
     }
 }
-PDF_API int pdf_fps(const float* xyz, int ld, int Bc, int N, int S, const int* start, int* idx, hipStream_t s) {
+PDF_API int pdf_fps(const float* xyz, int ld, int Bc, int N, int S, const int* start, int* idx, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (N <= 0 || S <= 0 || N > FPS_THREADS * FPS_MAXPT || ld < 3) return PDF_E_BADARG;
     if (Bc <= 0) return 0;
     static const bool wave_form = getenv("PDF_FPS_WAVE") == nullptr || atoi(getenv("PDF_FPS_WAVE")) != 0;

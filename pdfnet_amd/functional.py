@@ -2373,8 +2373,8 @@ def _pair(dst, l, r):
     dst[0], dst[1] = ptr(l), ptr(r)
 
 
-def _mesh_lin(dst, l, r):
-    _pair(dst.w, l.weight, r.weight)
+def _mesh_lin(dst, wf, l, r):
+    _pair(getattr(dst, wf), l.weight, r.weight)
     _pair(dst.b, l.bias, r.bias)
 
 
@@ -2392,8 +2392,9 @@ def mesh_level_params(layer):
     return gcn, self_, cross
 
 
-_MESH_GCN_KEYS = ('fc1', 'fc2', 'sc', 'n2', 'n3')
-_MESH_ATT_KEYS = ('ln', 'q', 'k', 'v', 'fc', 'ffln', 'f1', 'f2')
+# (field of PdfMeshGcn / PdfMeshAttn, name of its weight pair: `w` of a PdfMeshLin, `g` (gamma) of a PdfMeshLN; the bias pair is `b` in both)
+_MESH_GCN_KEYS = (('fc1', 'w'), ('fc2', 'w'), ('sc', 'w'), ('n2', 'g'), ('n3', 'g'))
+_MESH_ATT_KEYS = (('ln', 'g'), ('q', 'w'), ('k', 'w'), ('v', 'w'), ('fc', 'w'), ('ffln', 'g'), ('f1', 'w'), ('f2', 'w'))
 
 
 def _mesh_args(layer, x, save, p, out, tape, qkv):
@@ -2412,12 +2413,12 @@ def _mesh_args(layer, x, save, p, out, tape, qkv):
     a.ell_w = bl.ell_col.shape[1]
     gcn, self_, cross = mesh_level_params(layer)
     for i, blk in enumerate(gcn):
-        for k in _MESH_GCN_KEYS:
-            _mesh_lin(getattr(a.gcn[i], k), *blk[k])
+        for k, wf in _MESH_GCN_KEYS:
+            _mesh_lin(getattr(a.gcn[i], k), wf, *blk[k])
         a.gcn[i].seed = next_seed() if p > 0 else 0          # (drawn in the order the unfused path draws them: same masks)
     for dst, src in ((a.self_, self_), (a.cross, cross)):
-        for k in _MESH_ATT_KEYS:
-            _mesh_lin(getattr(dst, k), *src[k])
+        for k, wf in _MESH_ATT_KEYS:
+            _mesh_lin(getattr(dst, k), wf, *src[k])
         for k in ('seed_att', 'seed_z', 'seed_t', 'seed_x'):
             setattr(dst, k, next_seed() if p > 0 else 0)
     return a
@@ -2441,7 +2442,7 @@ def mesh_level_forward(layer, x, training=False, save=False):
 
 
 def _mesh_param_list(layer):
-    """Every parameter tensor the level uses, once, in a fixed order; and for each (group, index, key, hand, 'w' | 'b') where its gradient goes."""
+    """Every parameter tensor the level uses, once, in a fixed order; and for each (group, index, key, hand, 'w' | 'g' | 'b') where its gradient goes."""
     gcn, self_, cross = mesh_level_params(layer)
     seen, tensors, slots = {}, [], []
 
@@ -2452,14 +2453,14 @@ def _mesh_param_list(layer):
             slots.append([])
         slots[seen[id(t)]].append(where)
     for i, blk in enumerate(gcn):
-        for k in _MESH_GCN_KEYS:
+        for k, wf in _MESH_GCN_KEYS:
             for hnd, m in enumerate(blk[k]):
-                add(m.weight, ('ggcn', i, k, hnd, 'w'))
+                add(m.weight, ('ggcn', i, k, hnd, wf))
                 add(m.bias, ('ggcn', i, k, hnd, 'b'))
     for grp, src in (('gself', self_), ('gcross', cross)):
-        for k in _MESH_ATT_KEYS:
+        for k, wf in _MESH_ATT_KEYS:
             for hnd, m in enumerate(src[k]):
-                add(m.weight, (grp, None, k, hnd, 'w'))
+                add(m.weight, (grp, None, k, hnd, wf))
                 add(m.bias, (grp, None, k, hnd, 'b'))
     return tensors, slots
 

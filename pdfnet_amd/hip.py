@@ -19,12 +19,14 @@ _CT = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float,
        "unsigned long long": ctypes.c_ulonglong}
 
 
+def _text(path):
+    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+
+
 def parse_header(path=HEADER_PATH):
     """-> {name: (restype, [argtypes])} for every `int|long pdf_*(...)` prototype in the header."""
-    txt = open(path).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     protos = {}
-    for m in re.finditer(r"\b(int|long)\s+(pdf_\w+)\s*\(([^)]*)\)\s*;", txt):
+    for m in re.finditer(r"\b(int|long)\s+(pdf_\w+)\s*\(([^)]*)\)\s*;", _text(path)):
         ret, name, args = m.group(1), m.group(2), m.group(3)
         types = []
         for a in args.split(","):
@@ -40,58 +42,32 @@ def parse_header(path=HEADER_PATH):
     return protos
 
 
-class CallOpts(ctypes.Structure):
-    """PdfCallOpts of include/pdfnet_hip.h: the explicit options of the `_x` entry points (field for field)."""
-    _fields_ = [("op0_bf16", ctypes.c_void_p), ("op1_bf16", ctypes.c_void_p), ("out_bf16", ctypes.c_void_p), ("bn_x_bf16", ctypes.c_void_p),
-                ("stats_out", ctypes.c_void_p), ("stats_cap", ctypes.c_long), ("stats_tiles", ctypes.c_long), ("stats_rows", ctypes.c_long),
-                ("tile_stats", ctypes.c_void_p), ("tile_n", ctypes.c_long), ("tile_rows", ctypes.c_long),
-                ("in_scale", ctypes.c_void_p), ("in_shift", ctypes.c_void_p), ("op1_bf16_t", ctypes.c_void_p), ("ws", ctypes.c_void_p), ("ws_floats", ctypes.c_long),
-                ("wino_v", ctypes.c_void_p)]
+def parse_structs(path=HEADER_PATH):
+    """-> {name: ctypes.Structure class} for every `typedef struct Name { ... } Name;` of the header, in its order and with its field names.
+    Fields: a pointer (void* here), int / long / float / unsigned long long, an earlier struct; `a, b` declarator lists and `[n]` arrays.
+    Anything else raises: a layout is never guessed."""
+    txt, structs = _text(path), {}
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", txt):
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in m.group(2).split(";"))):
+            try:
+                first, *more = decl.split(",")
+                base, star, name, dim = re.fullmatch(r"(?:const )?([\w ]+?) ?(\*?) ?(\w+)(?:\[(\d+)\])?", first).groups()
+                ct = ctypes.c_void_p if star else _CT.get(base) or structs[base]
+                names = [(name, dim)] + [re.fullmatch(r" ?(\w+)(?:\[(\d+)\])?", d).groups() for d in more]
+                if star and more:                    # `float* a, b`: b is no pointer -- not written in this header, not bound
+                    raise KeyError(decl)
+            except (AttributeError, KeyError):       # no match / unknown type
+                raise ImportError("pdfnet_amd: %s: cannot bind field `%s` of %s" % (path, decl, m.group(1)))
+            fields += [(n, ct * int(d) if d else ct) for n, d in names]
+        structs[m.group(1)] = type(m.group(1), (ctypes.Structure,), {"_fields_": fields})
+    if len(structs) != len(re.findall(r"\b(?:struct|union)\b[^;(]*\{", txt)):
+        raise ImportError("pdfnet_amd: %s has a struct / union this binding cannot parse" % path)
+    return structs
 
 
-_P2 = ctypes.c_void_p * 2
-
-
-class MeshLin(ctypes.Structure):
-    """PdfMeshLin / PdfMeshLinG / PdfMeshLN / PdfMeshLNG of include/pdfnet_hip.h: a (weight, bias) or (gamma, beta) pair per hand."""
-    _fields_ = [("w", _P2), ("b", _P2)]
-
-
-class MeshGcn(ctypes.Structure):
-    _fields_ = [("fc1", MeshLin), ("fc2", MeshLin), ("sc", MeshLin), ("n2", MeshLin), ("n3", MeshLin), ("seed", ctypes.c_ulonglong)]
-
-
-class MeshAttn(ctypes.Structure):
-    _fields_ = [("ln", MeshLin), ("q", MeshLin), ("k", MeshLin), ("v", MeshLin), ("fc", MeshLin), ("ffln", MeshLin), ("f1", MeshLin), ("f2", MeshLin),
-                ("seed_att", ctypes.c_ulonglong), ("seed_z", ctypes.c_ulonglong), ("seed_t", ctypes.c_ulonglong), ("seed_x", ctypes.c_ulonglong)]
-
-
-class MeshGcnG(ctypes.Structure):
-    _fields_ = [("fc1", MeshLin), ("fc2", MeshLin), ("sc", MeshLin), ("n2", MeshLin), ("n3", MeshLin)]
-
-
-class MeshAttnG(ctypes.Structure):
-    _fields_ = [("ln", MeshLin), ("q", MeshLin), ("k", MeshLin), ("v", MeshLin), ("fc", MeshLin), ("ffln", MeshLin), ("f1", MeshLin), ("f2", MeshLin)]
-
-
-class MeshLevel(ctypes.Structure):
-    """PdfMeshLevel of include/pdfnet_hip.h (field for field; the library's sizeof is checked at load)."""
-    _fields_ = [("level", ctypes.c_int), ("B", ctypes.c_int), ("training", ctypes.c_int), ("cin0", ctypes.c_int), ("p", ctypes.c_float),
-                ("step", ctypes.c_void_p), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("ell_col", _P2), ("ell_val", _P2), ("ell_colT", _P2), ("ell_valT", _P2), ("ell_w", ctypes.c_int),
-                ("gcn", MeshGcn * 4), ("self_", MeshAttn), ("cross", MeshAttn),
-                ("tape", ctypes.c_void_p), ("qkv", ctypes.c_void_p), ("dout", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("gtape", ctypes.c_void_p),
-                ("ggcn", MeshGcnG * 4), ("gself", MeshAttnG), ("gcross", MeshAttnG), ("wg_ws", ctypes.c_void_p), ("wg_ws_floats", ctypes.c_long)]
-
-
-class MeshLoss(ctypes.Structure):
-    """PdfMeshLoss of include/pdfnet_hip.h (field for field)."""
-    _fields_ = [(k, ctypes.c_void_p) for k in ("vp", "v2p", "hd3", "hd2", "r")] + [(k, _P2) for k in ("vgt", "jgt", "v2gt", "lmsgt")] + \
-               [(k, ctypes.c_void_p) for k in ("ind", "K", "valid")] + \
-               [("reg", _P2), ("faces", ctypes.c_void_p), ("perm", _P2), ("B", ctypes.c_int), ("Fc", ctypes.c_int), ("size", ctypes.c_int),
-                ("down", ctypes.c_int), ("part", ctypes.c_void_p), ("out", ctypes.c_void_p), ("coef", ctypes.c_float * 12), ("gmp", ctypes.c_void_p),
-                ("edge_grad", ctypes.c_int)] + \
-               [(k, ctypes.c_void_p) for k in ("dvp", "dv2p", "dhd3", "dhd2", "dr")]
+STRUCTS = parse_structs()          # built once at import; a call only fills fields
+CallOpts, MeshLevel, MeshLoss = (STRUCTS[n] for n in ("PdfCallOpts", "PdfMeshLevel", "PdfMeshLoss"))
 
 
 class _Lib:
@@ -106,15 +82,10 @@ class _Lib:
             fn = getattr(self.cdll, name)          # AttributeError if the .so does not export it
             fn.restype = ret
             fn.argtypes = args
-        if self.cdll.pdf_debug_callopts_size() != ctypes.sizeof(CallOpts):
-            raise ImportError("pdfnet_amd: PdfCallOpts of %s has %d bytes, this binding's has %d -- rebuild the library"
-                              % (LIB_PATH, self.cdll.pdf_debug_callopts_size(), ctypes.sizeof(CallOpts)))
-        if self.cdll.pdf_debug_mesh_loss_size() != ctypes.sizeof(MeshLoss):
-            raise ImportError("pdfnet_amd: PdfMeshLoss of %s has %d bytes, this binding's has %d -- rebuild the library"
-                              % (LIB_PATH, self.cdll.pdf_debug_mesh_loss_size(), ctypes.sizeof(MeshLoss)))
-        if self.cdll.pdf_debug_mesh_level_size() != ctypes.sizeof(MeshLevel):
-            raise ImportError("pdfnet_amd: PdfMeshLevel of %s has %d bytes, this binding's has %d -- rebuild the library"
-                              % (LIB_PATH, self.cdll.pdf_debug_mesh_level_size(), ctypes.sizeof(MeshLevel)))
+        for cls, fn in ((CallOpts, "pdf_debug_callopts_size"), (MeshLoss, "pdf_debug_mesh_loss_size"), (MeshLevel, "pdf_debug_mesh_level_size")):
+            if getattr(self.cdll, fn)() != ctypes.sizeof(cls):
+                raise ImportError("pdfnet_amd: %s of %s has %d bytes, this binding's has %d -- rebuild the library"
+                                  % (cls.__name__, LIB_PATH, getattr(self.cdll, fn)(), ctypes.sizeof(cls)))
 
     def __getattr__(self, name):
         fn = getattr(self.cdll, name)

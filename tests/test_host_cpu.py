@@ -386,3 +386,33 @@ def test_committed_bench_line_keeps_the_drivers_contract():
     assert c["kind"] in ("port", "reference") and c["unit"] == "images/s" and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
     a = d["arithmetic"]                                                                                 # x3 is disclosed, with the all-native step beside it
     assert 1 <= a["x3_mode"] <= 7 and a["native_fp32_mfma_step"]["images_per_s"] > 0 and "native fp32 MFMA" in a["everything_else"]
+
+
+def test_ctypes_structures_have_the_layout_the_c_compiler_gives_the_header(tmp_path):
+    """hip.py builds its ctypes.Structure classes from the `typedef struct` blocks of include/pdfnet_hip.h; the library is compiled against the
+    same header.  What is left to go wrong is the binding's reading of C (a `long` taken for an `int`, a dropped array bound, a skipped
+    struct): a C99 program prints sizeof and, per field, offsetof and sizeof as gcc lays the header out, and every generated class must agree."""
+    import subprocess
+    from pdfnet_amd import hip
+    assert list(hip.STRUCTS) == ["PdfCallOpts", "PdfMeshLin", "PdfMeshLN", "PdfMeshGcn", "PdfMeshAttn", "PdfMeshLinG", "PdfMeshLNG", "PdfMeshGcnG",
+                                 "PdfMeshAttnG", "PdfMeshLevel", "PdfMeshLoss"]       # every typedef of the header: none skipped
+    assert (hip.CallOpts, hip.MeshLevel, hip.MeshLoss) == tuple(hip.STRUCTS[n] for n in ("PdfCallOpts", "PdfMeshLevel", "PdfMeshLoss"))
+    src = ['#include <stddef.h>', '#include <stdio.h>', '#include "pdfnet_hip.h"', 'int main(void) {']
+    got = {}
+    for name, cls in hip.STRUCTS.items():
+        src.append('    printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        got[name] = (ctypes.sizeof(cls),)
+        assert len(cls._fields_) >= 2
+        for f, ct in cls._fields_:
+            src.append('    printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (name, f, name, f, name, f))
+            got[name + "." + f] = (getattr(cls, f).offset, ctypes.sizeof(ct))
+    src += ['    return 0;', '}', '']
+    c_file, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
+    open(c_file, "w").write("\n".join(src))
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), c_file, "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    want = {l.split()[0]: tuple(int(v) for v in l.split()[1:]) for l in out.splitlines()}
+    assert set(want) == set(got)
+    for k in want:
+        assert got[k] == want[k], (k, got[k], want[k])
