@@ -95,8 +95,7 @@ int* pdf_ticket_counters(int n);
 #define PDF_SCRATCH_RING (1L << 26)
 #define PDF_SCRATCH_MAX (1L << 22)
 float* pdf_scratch(long floats);
-// bf16 shadows handed to the NEXT entry-point call of this thread (pdf_set_bf16_operands / pdf_set_bf16_output, elementwise.hip):
-// every GEMM-family entry point takes (and clears) the operand pair first thing, the BatchNorm / pyramid entry points the output.
+// bf16 packing: the shadows (PdfCallOpts below) and the x3 components are written with these
 typedef __bf16 pdf_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float pdf_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned int pdf_pk_bf16(float a, float b) {      // two floats -> packed bf16 pair, round-to-nearest-even
@@ -120,8 +119,22 @@ __device__ __forceinline__ void pdf_x3_store2(unsigned short* base, long o, long
     *reinterpret_cast<unsigned*>(base + o + cs) = m;
     *reinterpret_cast<unsigned*>(base + o + 2 * cs) = l;
 }
-// PdfCallOpts (pdfnet_hip.h): everything a call may take beyond its positional arguments.  The `_x` form of an entry point takes it explicitly; the
-// plain form takes (and clears) the thread's hand-over slots FIRST THING, so no return path leaves a slot armed.
-PdfCallOpts pdf_tls_take_all();                      // the thread's armed slots, cleared
-void pdf_tls_publish(const PdfCallOpts& o);          // stats_tiles / stats_rows -> pdf_stats_result_*
-
+// PdfCallOpts (pdfnet_hip.h): everything a call may take beyond its positional arguments.  An entry point that takes options has ONE body,
+// `int name_impl(positional arguments..., void* stream, PdfCallOpts& co)`, and two exported one-line forms that forward to it through the two
+// helpers below -- the only places that know the calling conventions.
+// `_x` form: opts == NULL means an all-zero block; stats_tiles / stats_rows are zeroed before the body looks at an argument; the thread's
+// hand-over slots are not touched.
+template <class F, class... A> static inline int pdf_call_x(PdfCallOpts* opts, F impl, A... a) {
+    PdfCallOpts none = {};
+    PdfCallOpts& co = opts != nullptr ? *opts : none;
+    co.stats_tiles = co.stats_rows = 0;
+    return impl(a..., co);
+}
+// plain form: take AND CLEAR every slot the pdf_set_* functions armed on this thread first thing (constructor), so no return path of the body
+// leaves one armed; afterwards publish stats_tiles / stats_rows for pdf_stats_result_* (destructor).  The slots themselves are private to
+// elementwise.hip, which defines both.
+struct PdfPlainCall { PdfCallOpts co; PdfPlainCall(); ~PdfPlainCall(); };
+template <class F, class... A> static inline int pdf_call_plain(F impl, A... a) {
+    PdfPlainCall call;
+    return impl(a..., call.co);
+}

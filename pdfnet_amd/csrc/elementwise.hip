@@ -618,8 +618,9 @@ PDF_API int pdf_set_bn_tile_stats(const float* part, long tiles, long rows_per_t
 PDF_API int pdf_set_input_affine_relu(const float* scale, const float* shift) { tl_opts.in_scale = scale; tl_opts.in_shift = shift; return 0; }
 PDF_API long pdf_stats_result_tiles(void) { return tl_res_tiles; }
 PDF_API long pdf_stats_result_rows(void) { return tl_res_rows; }
-PdfCallOpts pdf_tls_take_all() { PdfCallOpts o = tl_opts; tl_opts = PdfCallOpts{}; o.stats_tiles = o.stats_rows = 0; tl_res_tiles = tl_res_rows = 0; return o; }
-void pdf_tls_publish(const PdfCallOpts& o) { tl_res_tiles = o.stats_tiles; tl_res_rows = o.stats_rows; }
+// the two halves of the plain calling convention (pdf_call_plain, common.h)
+PdfPlainCall::PdfPlainCall() : co(tl_opts) { tl_opts = PdfCallOpts{}; co.stats_tiles = co.stats_rows = 0; tl_res_tiles = tl_res_rows = 0; }
+PdfPlainCall::~PdfPlainCall() { tl_res_tiles = co.stats_tiles; tl_res_rows = co.stats_rows; }
 // how many hand-over slots of the calling thread are armed (tests: a rejected call must leave none)
 PDF_API int pdf_debug_armed_slots(void) {
     const PdfCallOpts& o = tl_opts;

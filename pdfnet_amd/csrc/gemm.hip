@@ -1363,28 +1363,24 @@ PDF_API int pdf_debug_shadow_operands() { return g_shadow_operands; }       // i
 PDF_API int pdf_debug_last_tile() { return g_last_tile; }
 PDF_API int pdf_debug_igemm_launches() { return g_igemm_launches; }
 
-// BatchNorm statistics out of a forward GEMM's epilogue (IGemm::stat): the request of the NEXT conv2d / linear forward call of
-// this thread (pdf_set_stats_output) and what that call produced (pdf_stats_result_tiles / _rows; 0 tiles: the launch it chose
-// has no statistics epilogue -- the caller then runs the ordinary statistics pass).
-struct StatReq { float* part; long cap; };
-static thread_local PdfCallOpts* tl_cur = nullptr;   // the call in progress on this thread (stat_plan publishes the layout it chose into it)
-struct CurCall { PdfCallOpts* prev; explicit CurCall(PdfCallOpts& co) : prev(tl_cur) { tl_cur = &co; } ~CurCall() { tl_cur = prev; } };
-static void stat_result(long tiles, long rows) { if (tl_cur != nullptr) { tl_cur->stats_tiles = tiles; tl_cur->stats_rows = rows; } }
-// the launch about to be issued uses row blocks of BM rows: keep the request if the partials fit, and publish the layout
-static void stat_plan(IGemm& g, long cap, int BM) {
-    if (g.stat == nullptr) return;
+// BatchNorm statistics out of a forward GEMM's epilogue (IGemm::stat): a conv2d / linear forward hands its own PdfCallOpts to
+// launch_igemm, which reads the request from it (stats_out, stats_cap) and writes back what the launch it chose produces
+// (stats_tiles / stats_rows; 0 tiles: that launch has no statistics epilogue -- the caller then runs the ordinary statistics pass).
+// The launch about to be issued uses row blocks of BM rows: keep the request if the partials fit, and report the layout.
+static void stat_plan(IGemm& g, PdfCallOpts* co, int BM) {
+    if (g.stat == nullptr) return;                      // (g.stat != nullptr implies co != nullptr: launch_igemm sets it from co only)
     const long tiles = cdiv(g.M, BM);
-    if (!g.plain_out || g.ps_cout > 0 || g.accum || tiles * g.N * 2 > cap) { g.stat = nullptr; return; }
-    stat_result(tiles, BM);
+    if (!g.plain_out || g.ps_cout > 0 || g.accum || tiles * g.N * 2 > co->stats_cap) { g.stat = nullptr; return; }
+    co->stats_tiles = tiles; co->stats_rows = BM;
 }
 
-// groups == 2: paired launch (see IGemm::B1), blockIdx.y selects the group
-static int launch_igemm(IGemm& g, hipStream_t s, int groups = 1, long stat_cap = 0) {
+// groups == 2: paired launch (see IGemm::B1), blockIdx.y selects the group.  co: the options of a forward call that may ask for
+// statistics (honoured for groups == 1 only); nullptr for every other caller.
+static int launch_igemm(IGemm& g, hipStream_t s, int groups = 1, PdfCallOpts* co = nullptr) {
     if (g.M <= 0 || g.N <= 0 || g.K <= 0) return 0;
     g.gm = env_int(ENV_IG_GROUPM, 4);               // (round 5: L2-miss reads of the 64x64 family 112 -> 81 MB per launch, of the transposed convolutions 1,539 -> 583; times unchanged -- profiles/r05_groupm.txt)
     ++g_igemm_launches;
-    if (groups > 1) g.stat = nullptr;
-    float* const stat_req = g.stat;
+    float* const stat_req = (co != nullptr && groups == 1) ? co->stats_out : nullptr;
     g.stat = nullptr;                                   // (the streaming / split-K launches below have no statistics epilogue; bf16: whole tiles only)
     bool fast = (g.Cin % 16 == 0) && (g.lda % 4 == 0) && (g.ldb % 4 == 0) && aligned16(g.A) && aligned16(g.B);
     if (g.b_kn) fast = fast && (g.N % 4 == 0) && (g.btap % 4 == 0);
@@ -1418,12 +1414,12 @@ static int launch_igemm(IGemm& g, hipStream_t s, int groups = 1, long stat_cap =
         // BatchNorm statistics out of the fp32 accumulators: the bf16 kernels take them in their whole-tile epilogue only
         const int bm16 = igemm_bf16_tile_rows(g, groups);
         if (g.C16 != nullptr && (groups != 1 || g.cbytes == 0 || g.M % bm16 != 0 || g.accum)) return PDF_E_BADARG;      // bf16 output: whole tiles only
-        if (stat_req != nullptr && groups == 1 && g.cbytes != 0 && g.M % bm16 == 0 && env_int(ENV_IG_BF16_STATS, 1)) { g.stat = stat_req; stat_plan(g, stat_cap, bm16); }
+        if (stat_req != nullptr && groups == 1 && g.cbytes != 0 && g.M % bm16 == 0 && env_int(ENV_IG_BF16_STATS, 1)) { g.stat = stat_req; stat_plan(g, co, bm16); }
         const int rc = launch_igemm_bf16(g, s, groups);
         if (rc < 0) return -rc;
         if (rc == 1) { g_last_tile = 16; return 0; }
         g.stat = nullptr;
-        stat_result(0, 0);
+        if (co != nullptr) co->stats_tiles = co->stats_rows = 0;
     }
     if (g.C16 != nullptr) return PDF_E_BADARG;             // (only the bf16 kernels write a bf16 output)
     if (g.A == nullptr) return PDF_E_BADARG;               // (... and only they read a bf16-only operand)
@@ -1478,7 +1474,7 @@ static int launch_igemm(IGemm& g, hipStream_t s, int groups = 1, long stat_cap =
     for (int t = 0; halo && t < 9; ++t) halo = g.dy[t] >= -1 && g.dy[t] <= 1 && g.dx[t] >= -1 && g.dx[t] <= 1;
     g.stat = stat_req;
     if (halo) {
-        stat_plan(g, stat_cap, 128);
+        stat_plan(g, co, 128);
         const dim3 grid((g.M / 128) * cdiv(g.N, 128));
         const bool buf = g.abytes != 0 && env_int(ENV_IG_BUF, 1);
         KTimer kt(g.b_kn ? (buf ? "igemm_halo3x3<true, true>" : "igemm_halo3x3<true, false>") : (buf ? "igemm_halo3x3<false, true>" : "igemm_halo3x3<false, false>"),
@@ -1490,23 +1486,23 @@ static int launch_igemm(IGemm& g, hipStream_t s, int groups = 1, long stat_cap =
         g_last_tile = 128128;
     }
     else if (g.N > 64 && t128 >= env_int(ENV_IG_T128, 600) && !short_k) {
-        stat_plan(g, stat_cap, 128);
+        stat_plan(g, co, 128);
         const int dma = env_int(ENV_IG_DMA128, 0);
         if (!(dma > 0 && fast && g.batch == 0 && launch_igemm_dma(g, 128, dma - 1, groups, 0, s)))
             launch_igemm_tile<128, 128, 2, 2>(g, fast, dim3(cdiv(g.M, 128) * cdiv(g.N, 128), groups), s);
         g_last_tile = 128128;
     }
     else if (g.N <= 64 && (long)cdiv(g.M, 128) * groups >= env_int(ENV_IG_T128, 600))
-        stat_plan(g, stat_cap, 128), launch_igemm_tile<128, 64, 4, 1>(g, fast, dim3(cdiv(g.M, 128) * cdiv(g.N, 64), groups), s), g_last_tile = 128064;   // (K-step 32: no gain here)
+        stat_plan(g, co, 128), launch_igemm_tile<128, 64, 4, 1>(g, fast, dim3(cdiv(g.M, 128) * cdiv(g.N, 64), groups), s), g_last_tile = 128064;   // (K-step 32: no gain here)
     else if (fast && (long)cdiv(g.M, 64) * cdiv(g.N, 64) * groups < 96 && g.K >= 512 && env_int(ENV_IG_T32, 1)) {
         // a handful of 64x64 tiles with a long reduction (M = 64 centre windows, the mesh decoder's 1024-wide layers): latency
         // bound on a few CUs -- 32x32 tiles put 4x as many blocks on the chip (one wave each)
-        stat_plan(g, stat_cap, 32);
+        stat_plan(g, co, 32);
         launch_igemm_tile<32, 32, 1, 1>(g, fast, dim3(cdiv(g.M, 32) * cdiv(g.N, 32), groups), s), g_last_tile = 32032;
     }
     else
     {
-        stat_plan(g, stat_cap, 64);
+        stat_plan(g, co, 64);
         const dim3 grid(cdiv(g.M, 64) * cdiv(g.N, 64), groups);
         const int dma = env_int(ENV_IG_DMA, 0);
         // K-step 32 for the small tile: its 8 MFMAs per wave and 16-wide step leave the barrier exposed (l4 3x3: 62 -> 72 TFLOP/s)
@@ -1586,8 +1582,6 @@ static void conv_taps(IGemm& g, int KH, int KW, int pad, int dil) {
         }
 }
 
-struct Shadows { const void* op0; const void* op1; };
-
 // Linear / 1x1: y[M][N] = act(x[M][K] w[N][K]^T + b).  Reference: nn.Linear / 1x1 nn.Conv2d call sites
 // (e.g. model_attn/gcn.py:66, intaghand_encoder.py:48-103 netR_*, :205-219 SFT convs).
 static IGemm linear_desc(const float* x, const float* w, const float* bias, float* y,
@@ -1600,60 +1594,75 @@ static IGemm linear_desc(const float* x, const float* w, const float* bias, floa
     return g;
 }
 static int pdf_linear_fwd_impl(const float* x, const float* w, const float* bias, float* y,
-                           int M, int N, int K, int ldx, int ldw, int ldy, int act, hipStream_t s, PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};
-    const StatReq sr = {co.stats_out, co.stats_cap};
-    const CurCall cur(co);
+                           int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     IGemm g = linear_desc(x, w, bias, y, M, N, K, ldx, ldw, ldy, act);
-    g.A16 = sh.op0; g.B16 = sh.op1;
-    g.stat = sr.part;
+    g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
     g.a_scale = co.in_scale; g.a_shift = co.in_shift;
-    return launch_igemm(g, s, 1, sr.cap);
+    return launch_igemm(g, s, 1, &co);
 }
 PDF_API int pdf_linear_fwd_x(const float* x, const float* w, const float* bias, float* y,
-                           int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_fwd_impl(x, w, bias, y, M, N, K, ldx, ldw, ldy, act, s, co); }
+                           int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_linear_fwd_impl, x, w, bias, y, M, N, K, ldx, ldw, ldy, act, stream);
+}
 PDF_API int pdf_linear_fwd(const float* x, const float* w, const float* bias, float* y,
-                           int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_fwd_impl(x, w, bias, y, M, N, K, ldx, ldw, ldy, act, s, co); pdf_tls_publish(co); return rc; }
+                           int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream) {
+    return pdf_call_plain(pdf_linear_fwd_impl, x, w, bias, y, M, N, K, ldx, ldw, ldy, act, stream);
+}
 
 // Two same-shaped layers with their own parameters in ONE launch (the left / right hand branches of the mesh decoder,
 // DualGraph.py:83-84, inter_attn.py:66-67): rows [0, M) of x / y belong to (w0, b0), rows [M, 2M) to (w1, b1).
 static int pdf_linear_fwd_pair_impl(const float* x, const float* w0, const float* w1, const float* b0, const float* b1, float* y,
-                                int M, int N, int K, int ldx, int ldw, int ldy, int act, hipStream_t s, PdfCallOpts& co) {
+                                int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     IGemm g = linear_desc(x, w0, b0, y, M, N, K, ldx, ldw, ldy, act);
     g.B1 = w1; g.bias1 = b1; g.gsA = (long)M * ldx; g.gsC = (long)M * ldy;
     return launch_igemm(g, s, 2);
 }
 PDF_API int pdf_linear_fwd_pair_x(const float* x, const float* w0, const float* w1, const float* b0, const float* b1, float* y,
-                                int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_fwd_pair_impl(x, w0, w1, b0, b1, y, M, N, K, ldx, ldw, ldy, act, s, co); }
+                                int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_linear_fwd_pair_impl, x, w0, w1, b0, b1, y, M, N, K, ldx, ldw, ldy, act, stream);
+}
 PDF_API int pdf_linear_fwd_pair(const float* x, const float* w0, const float* w1, const float* b0, const float* b1, float* y,
-                                int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_fwd_pair_impl(x, w0, w1, b0, b1, y, M, N, K, ldx, ldw, ldy, act, s, co); pdf_tls_publish(co); return rc; }
+                                int M, int N, int K, int ldx, int ldw, int ldy, int act, void* stream) {
+    return pdf_call_plain(pdf_linear_fwd_pair_impl, x, w0, w1, b0, b1, y, M, N, K, ldx, ldw, ldy, act, stream);
+}
 
 // dx[M][K] = dy[M][N] w[N][K]: the weight is read in its forward [N][K] storage (no transposed copy)
 static int pdf_linear_bwd_data_impl(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int ldw, int lddx,
-                                hipStream_t s, PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};
+                                void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     IGemm g = linear_desc(dy, w, nullptr, dx, M, K, N, lddy, ldw, lddx, 0);
     g.b_kn = 1; g.btap = 0;
-    g.A16 = sh.op0; g.B16 = sh.op1;
+    g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
     if (ldw == K) { g.B16T = co.op1_bf16_t; g.ldbT = N; }   // (the transposed shadow is of the dense [N][K] matrix)
     return launch_igemm(g, s);
 }
 PDF_API int pdf_linear_bwd_data_x(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int ldw, int lddx,
-                                void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_data_impl(dy, w, dx, M, N, K, lddy, ldw, lddx, s, co); }
+                                void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_linear_bwd_data_impl, dy, w, dx, M, N, K, lddy, ldw, lddx, stream);
+}
 PDF_API int pdf_linear_bwd_data(const float* dy, const float* w, float* dx, int M, int N, int K, int lddy, int ldw, int lddx,
-                                void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_data_impl(dy, w, dx, M, N, K, lddy, ldw, lddx, s, co); pdf_tls_publish(co); return rc; }
+                                void* stream) {
+    return pdf_call_plain(pdf_linear_bwd_data_impl, dy, w, dx, M, N, K, lddy, ldw, lddx, stream);
+}
 
 static int pdf_linear_bwd_data_pair_impl(const float* dy, const float* w0, const float* w1, float* dx, int M, int N, int K,
-                                     int lddy, int ldw, int lddx, hipStream_t s, PdfCallOpts& co) {
+                                     int lddy, int ldw, int lddx, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     IGemm g = linear_desc(dy, w0, nullptr, dx, M, K, N, lddy, ldw, lddx, 0);
     g.b_kn = 1; g.btap = 0;
     g.B1 = w1; g.bias1 = nullptr; g.gsA = (long)M * lddy; g.gsC = (long)M * lddx;
     return launch_igemm(g, s, 2);
 }
 PDF_API int pdf_linear_bwd_data_pair_x(const float* dy, const float* w0, const float* w1, float* dx, int M, int N, int K,
-                                     int lddy, int ldw, int lddx, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_data_pair_impl(dy, w0, w1, dx, M, N, K, lddy, ldw, lddx, s, co); }
+                                     int lddy, int ldw, int lddx, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_linear_bwd_data_pair_impl, dy, w0, w1, dx, M, N, K, lddy, ldw, lddx, stream);
+}
 PDF_API int pdf_linear_bwd_data_pair(const float* dy, const float* w0, const float* w1, float* dx, int M, int N, int K,
-                                     int lddy, int ldw, int lddx, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_data_pair_impl(dy, w0, w1, dx, M, N, K, lddy, ldw, lddx, s, co); pdf_tls_publish(co); return rc; }
+                                     int lddy, int ldw, int lddx, void* stream) {
+    return pdf_call_plain(pdf_linear_bwd_data_pair_impl, dy, w0, w1, dx, M, N, K, lddy, ldw, lddx, stream);
+}
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1873,10 +1882,8 @@ __global__ __launch_bounds__(256) void stem7x7_fwd_kernel(const float* __restric
 
 static int pdf_conv2d_fwd_impl(const float* x, const float* w, const float* bias, float* y,
                            int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                           int stride, int pad, int OH, int OW, int ldy, int act, hipStream_t s, PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};
-    const StatReq sr = {co.stats_out, co.stats_cap};
-    const CurCall cur(co);
+                           int stride, int pad, int OH, int OW, int ldy, int act, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     unsigned short* y16 = reinterpret_cast<unsigned short*>(co.out_bf16);      // bf16 storage mode: the output goes here INSTEAD of y
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
     if (y16 != nullptr && !(g_gemm_bf16 && Cout % 2 == 0 && ldy % 2 == 0)) return PDF_E_BADARG;
@@ -1896,8 +1903,8 @@ static int pdf_conv2d_fwd_impl(const float* x, const float* w, const float* bias
         const int cpb = (int)cdiv(total, nblk);
         nblk = (int)cdiv(total, cpb);
         KTimer kt("stem7x7_fwd_kernel", 2.0 * N * OH * OW * 64 * 147, 4.0 * N * ((double)H * W * 3 + (double)OH * OW * 64), s);
-        float* stat = (sr.part != nullptr && (long)nblk * 64 * 2 <= sr.cap) ? sr.part : nullptr;
-        if (stat != nullptr) stat_result(nblk, (long)cpb * 64);
+        float* stat = (co.stats_out != nullptr && (long)nblk * 64 * 2 <= co.stats_cap) ? co.stats_out : nullptr;
+        if (stat != nullptr) { co.stats_tiles = nblk; co.stats_rows = (long)cpb * 64; }
         hipLaunchKernelGGL(stem7x7_fwd_kernel, dim3(nblk), dim3(256), 0, s, x, w, y, N, H, W, OH, OW, ldy, act, cpb, stat);
         g_last_tile = 0;
         PDF_LAUNCH_CHECK();
@@ -1917,26 +1924,29 @@ static int pdf_conv2d_fwd_impl(const float* x, const float* w, const float* bias
     conv_taps(g, KH, KW, pad, 1);
     g.plain_in = (KH == 1 && KW == 1 && stride == 1 && pad == 0) ? 1 : 0;
     g.plain_out = 1; g.act = act;
-    g.A16 = sh.op0; g.B16 = sh.op1;
-    g.stat = sr.part;
+    g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
     g.C16 = y16;
-    return launch_igemm(g, s, 1, sr.cap);
+    return launch_igemm(g, s, 1, &co);
 }
 PDF_API int pdf_conv2d_fwd_x(const float* x, const float* w, const float* bias, float* y,
                            int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                           int stride, int pad, int OH, int OW, int ldy, int act, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, act, s, co); }
+                           int stride, int pad, int OH, int OW, int ldy, int act, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_conv2d_fwd_impl, x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, act, stream);
+}
 PDF_API int pdf_conv2d_fwd(const float* x, const float* w, const float* bias, float* y,
                            int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                           int stride, int pad, int OH, int OW, int ldy, int act, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, act, s, co); pdf_tls_publish(co); return rc; }
+                           int stride, int pad, int OH, int OW, int ldy, int act, void* stream) {
+    return pdf_call_plain(pdf_conv2d_fwd_impl, x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, act, stream);
+}
 
 
 // Conv2d backward-data: dx[N,H,W,Cin] from dy[N,OH,OW,Cout] and the FORWARD weight w = [Cout][KH][KW][Cin], read as
 // the [K = (tap, co)][N = ci] operand it is.  One launch per input-parity class so a stride-s conv
-// never multiplies zeros.  dx must be zero-filled by the caller when stride > kernel (1x1 s2).
-static int conv2d_bwd_data(const float* dy, const float* w, float* dx,
-                           int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                           int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s, const PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};
+// never multiplies zeros.  dx must be zero-filled by the caller when stride > kernel (1x1 s2).  accumulate: the _add form below.
+static int pdf_conv2d_bwd_data_impl(const float* dy, const float* w, float* dx,
+                                int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
+                                int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
     if (accumulate && stride > 1) return PDF_E_BADARG;       // (every dx element must be written by exactly one launch)
     // Winograd: dx = the 3x3 convolution of dy (Cout channels) with the mirrored taps, Cin output channels
@@ -1955,7 +1965,7 @@ static int conv2d_bwd_data(const float* dy, const float* w, float* dx,
             if (g.QH <= 0 || g.QW <= 0) continue;
             g.M = N * g.QH * g.QW;
             g.sy = 1; g.sx = 1; g.accum = accumulate;
-            g.A16 = sh.op0; g.B16 = sh.op1;
+            g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
             g.B16T = co.op1_bf16_t; g.ldbT = KH * KW * Cout;
             // input row iy = qy*stride + py; contributing taps: (iy + pad - ky) % stride == 0, oy = (iy+pad-ky)/stride
             int T = 0;
@@ -1982,31 +1992,29 @@ static int conv2d_bwd_data(const float* dy, const float* w, float* dx,
     return 0;
 }
 
-static int pdf_conv2d_bwd_data_impl(const float* dy, const float* w, float* dx,
-                                int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                int stride, int pad, int OH, int OW, int lddy, hipStream_t s, PdfCallOpts& co) {
-    return conv2d_bwd_data(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, 0, s, co);
-}
 PDF_API int pdf_conv2d_bwd_data_x(const float* dy, const float* w, float* dx,
                                 int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
+                                int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_conv2d_bwd_data_impl, dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, 0, stream);
+}
 PDF_API int pdf_conv2d_bwd_data(const float* dy, const float* w, float* dx,
                                 int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                int stride, int pad, int OH, int OW, int lddy, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
+                                int stride, int pad, int OH, int OW, int lddy, void* stream) {
+    return pdf_call_plain(pdf_conv2d_bwd_data_impl, dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, 0, stream);
+}
 
 // dx += the same (stride 1): the gradient of a tensor with two consumers -- a ResNet block input feeds conv1 and the shortcut --
 // is accumulated by the second producer's epilogue instead of a separate add pass over both gradients
-static int pdf_conv2d_bwd_data_add_impl(const float* dy, const float* w, float* dx,
-                                    int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, hipStream_t s, PdfCallOpts& co) {
-    return conv2d_bwd_data(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, 1, s, co);
-}
 PDF_API int pdf_conv2d_bwd_data_add_x(const float* dy, const float* w, float* dx,
                                     int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_data_add_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
+                                    int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_conv2d_bwd_data_impl, dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, 1, stream);
+}
 PDF_API int pdf_conv2d_bwd_data_add(const float* dy, const float* w, float* dx,
                                     int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_data_add_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
+                                    int stride, int pad, int OH, int OW, int lddy, void* stream) {
+    return pdf_call_plain(pdf_conv2d_bwd_data_impl, dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, 1, stream);
+}
 
 
 // Split count of a weight-gradient launch: the candidate with the smallest modelled time (see launch_wgemm).
@@ -2191,25 +2199,30 @@ PDF_API long pdf_wgrad_workspace_floats(int M, int NI, int NJ) {
 
 // dW[N][K] (+)= dy[M][N]^T x[M][K]   (Linear / 1x1 weight gradient)
 static int pdf_linear_bwd_weight_impl(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
-                                  int M, int N, int K, int ldx, int lddy, int accumulate, hipStream_t s, PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};                       // op0: x, op1: dy
+                                  int M, int N, int K, int ldx, int lddy, int accumulate, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     WGemm g = {};
     g.P = dy; g.Q = x; g.M = M; g.NI = N; g.Cq = K; g.T = 1; g.ldp = lddy; g.ldq = ldx; g.ldw = K;
     g.plain_q = 1; g.H = 1; g.W = M; g.QH = 1; g.QW = M; g.sy = 1; g.sx = 1;
     g.dy[0] = 0; g.dx[0] = 0; g.wt[0] = 0;
-    g.Q16 = sh.op0; g.P16 = sh.op1;
+    g.Q16 = co.op0_bf16; g.P16 = co.op1_bf16;             // op0: x, op1: dy
     g.q_scale = co.in_scale; g.q_shift = co.in_shift;
     return launch_wgemm(g, dw, ws, ws_floats, accumulate, s, nullptr, db);
 }
 PDF_API int pdf_linear_bwd_weight_x(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
-                                  int M, int N, int K, int ldx, int lddy, int accumulate, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); }
+                                  int M, int N, int K, int ldx, int lddy, int accumulate, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_linear_bwd_weight_impl, x, dy, dw, db, ws, ws_floats, M, N, K, ldx, lddy, accumulate, stream);
+}
 PDF_API int pdf_linear_bwd_weight(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
-                                  int M, int N, int K, int ldx, int lddy, int accumulate, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
+                                  int M, int N, int K, int ldx, int lddy, int accumulate, void* stream) {
+    return pdf_call_plain(pdf_linear_bwd_weight_impl, x, dy, dw, db, ws, ws_floats, M, N, K, ldx, lddy, accumulate, stream);
+}
 
 
 // paired form of the above: rows [0, M) -> dw0, rows [M, 2M) -> dw1; ws >= 2 * pdf_wgrad_workspace_floats(M, N, K)
 static int pdf_linear_bwd_weight_pair_impl(const float* x, const float* dy, float* dw0, float* dw1, float* db0, float* db1,
-                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, hipStream_t s, PdfCallOpts& co) {
+                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     WGemm g = {};
     g.P = dy; g.Q = x; g.M = M; g.NI = N; g.Cq = K; g.T = 1; g.ldp = lddy; g.ldq = ldx; g.ldw = K;
     g.plain_q = 1; g.H = 1; g.W = M; g.QH = 1; g.QW = M; g.sy = 1; g.sx = 1;
@@ -2218,9 +2231,13 @@ static int pdf_linear_bwd_weight_pair_impl(const float* x, const float* dy, floa
     return launch_wgemm(g, dw0, ws, ws_floats, accumulate, s, dw1, db0, db1);
 }
 PDF_API int pdf_linear_bwd_weight_pair_x(const float* x, const float* dy, float* dw0, float* dw1, float* db0, float* db1,
-                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_linear_bwd_weight_pair_impl(x, dy, dw0, dw1, db0, db1, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); }
+                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_linear_bwd_weight_pair_impl, x, dy, dw0, dw1, db0, db1, ws, ws_floats, M, N, K, ldx, lddy, accumulate, stream);
+}
 PDF_API int pdf_linear_bwd_weight_pair(const float* x, const float* dy, float* dw0, float* dw1, float* db0, float* db1,
-                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_linear_bwd_weight_pair_impl(x, dy, dw0, dw1, db0, db1, ws, ws_floats, M, N, K, ldx, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
+                                       float* ws, long ws_floats, int M, int N, int K, int ldx, int lddy, int accumulate, void* stream) {
+    return pdf_call_plain(pdf_linear_bwd_weight_pair_impl, x, dy, dw0, dw1, db0, db1, ws, ws_floats, M, N, K, ldx, lddy, accumulate, stream);
+}
 
 
 // dW[Cout][KH][KW][Cin] (+)= sum over output pixels dy[m][co] * x[pos(m,tap)][ci]
@@ -2325,8 +2342,8 @@ __global__ __launch_bounds__(256) void stem7x7_wgrad_kernel(const float* __restr
 
 static int pdf_conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
                                   int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s, PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};                       // op0: x, op1: dy
+                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
     // Winograd F(4x4, 3x3) weight gradient (winograd.hip): fp32 mode, the caller handed a workspace (PdfCallOpts::ws), the layer qualifies
     if (!g_gemm_bf16 && co.ws != nullptr && dy != nullptr && OH == H && OW == W && ldx % 4 == 0 && lddy % 4 == 0 && aligned16(x) && aligned16(dy) &&
@@ -2335,7 +2352,7 @@ static int pdf_conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw
         return pdf_internal_conv3x3_winograd_wgrad(x, ldx, dy, lddy, dw, db, co.ws, N, H, W, Cin, Cout, accumulate,
                                                    (co.wino_v != nullptr && aligned16(co.wino_v) && pdf_internal_wino_v_offset(N, H, W, Cin, Cout) >= 0) ? co.wino_v : nullptr, s);
     // bf16 storage mode: dy exists only as bf16 (dy == NULL) -- the launch must be one the bf16 kernel takes with a shadow operand
-    if (dy == nullptr && (sh.op1 == nullptr || db != nullptr || !g_gemm_bf16 || Cin % 16 != 0 || Cout % 16 != 0 || lddy % 8 != 0)) return PDF_E_BADARG;
+    if (dy == nullptr && (co.op1_bf16 == nullptr || db != nullptr || !g_gemm_bf16 || Cin % 16 != 0 || Cout % 16 != 0 || lddy % 8 != 0)) return PDF_E_BADARG;
     if (Cin == 3 && Cout == 3 && KH == 3 && KW == 3 && stride == 1 && db == nullptr && (long)N * OH * OW >= (1L << 16) && ws_floats >= 81L * 64) {
         const int nblk = (int)min((long)1024, ws_floats / 81);
         KTimer kt("tiny_conv_wgrad_kernel<3, 3, 3, 3> + reduce_slabs_2d", 2.0 * N * OH * OW * 81, 4.0 * N * (H * W + OH * OW) * 3, s);
@@ -2386,15 +2403,21 @@ static int pdf_conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw
             int t = ky * KW + kx;
             g.dy[t] = (int)(ky - pad); g.dx[t] = (int)(kx - pad); g.wt[t] = t;
         }
-    g.Q16 = sh.op0; g.P16 = sh.op1;
+    g.Q16 = co.op0_bf16; g.P16 = co.op1_bf16;             // op0: x, op1: dy
     return launch_wgemm(g, dw, ws, ws_floats, accumulate, s, nullptr, db);
 }
 PDF_API int pdf_conv2d_bwd_weight_x(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
                                   int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_conv2d_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); }
+                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_conv2d_bwd_weight_impl, x, dy, dw, db, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy,
+                      accumulate, stream);
+}
 PDF_API int pdf_conv2d_bwd_weight(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
                                   int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_conv2d_bwd_weight_impl(x, dy, dw, db, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
+                                  int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream) {
+    return pdf_call_plain(pdf_conv2d_bwd_weight_impl, x, dy, dw, db, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy,
+                          accumulate, stream);
+}
 
 
 // ConvTranspose2d forward on NHWC: y[n, iy*s - pad + ky, ix*s - pad + kx, co] += x[n,iy,ix,ci] w[ci][co][ky][kx].
@@ -2403,20 +2426,19 @@ PDF_API int pdf_conv2d_bwd_weight(const float* x, const float* dy, float* dw, fl
 // otherwise (p3: k4 s2 p1, :603) one launch per output-parity class.
 static int pdf_deconv2d_fwd_impl(const float* x, const float* w, const float* bias, float* y,
                              int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                             int stride, int pad, int OH, int OW, int ldy, hipStream_t s, PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};                       // op0: x, op1: w
+                             int stride, int pad, int OH, int OW, int ldy, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
     if (!g_gemm_bf16 && co.ws != nullptr && ldx == Cin && ldy == Cout) {  // x3 form (gemm_x3.hip): kernel == stride, long reduction, workspace handed in
         const long need = pdf_internal_x3_deconv_workspace(N, H, W, Cin, Cout, KH, KW, stride, pad, 0);
         if (need > 0 && co.ws_floats >= need && ((uintptr_t)co.ws & 15) == 0) {
-            const CurCall cur(co);
             if (KH != stride || pad != 0) return pdf_internal_x3_deconv_general_fwd(x, w, bias, y, co.ws, N, H, W, Cin, Cout, KH, stride, pad, OH, OW, ldy, s);
             return pdf_internal_x3_deconv_fwd(x, w, bias, y, co.ws, N, H, W, Cin, Cout, KH, KW, stride, OH, OW, ldy, s);
         }
     }
     if (KH == stride && KW == stride && pad == 0) {
         IGemm g = {};
-        g.A = x; g.B = w; g.C = y; g.bias = bias; g.A16 = sh.op0; g.B16 = sh.op1;
+        g.A = x; g.B = w; g.C = y; g.bias = bias; g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
         g.M = N * H * W; g.N = KH * KW * Cout; g.K = Cin; g.Cin = Cin; g.lda = ldx; g.ldc = ldy;
         // columns n = (tap, co): w[ci][tap][co] is exactly a [K = ci][N] matrix
         g.ldb = KH * KW * Cout; g.b_kn = 1; g.btap = 0;
@@ -2429,7 +2451,7 @@ static int pdf_deconv2d_fwd_impl(const float* x, const float* w, const float* bi
     for (int py = 0; py < stride; ++py)
         for (int px = 0; px < stride; ++px) {
             IGemm g = {};
-            g.A = x; g.B = w; g.C = y; g.bias = bias; g.A16 = sh.op0; g.B16 = sh.op1;
+            g.A = x; g.B = w; g.C = y; g.bias = bias; g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
             g.N = Cout; g.Cin = Cin; g.lda = ldx; g.ldb = KH * KW * Cout; g.b_kn = 1; g.btap = Cout; g.ldc = ldy;
             g.H = H; g.W = W;
             g.QH = (OH - py + stride - 1) / stride; g.QW = (OW - px + stride - 1) / stride;
@@ -2459,29 +2481,32 @@ static int pdf_deconv2d_fwd_impl(const float* x, const float* w, const float* bi
 }
 PDF_API int pdf_deconv2d_fwd_x(const float* x, const float* w, const float* bias, float* y,
                              int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                             int stride, int pad, int OH, int OW, int ldy, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, s, co); }
+                             int stride, int pad, int OH, int OW, int ldy, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_deconv2d_fwd_impl, x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, stream);
+}
 PDF_API int pdf_deconv2d_fwd(const float* x, const float* w, const float* bias, float* y,
                              int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                             int stride, int pad, int OH, int OW, int ldy, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_fwd_impl(x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, s, co); pdf_tls_publish(co); return rc; }
+                             int stride, int pad, int OH, int OW, int ldy, void* stream) {
+    return pdf_call_plain(pdf_deconv2d_fwd_impl, x, w, bias, y, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, ldy, stream);
+}
 
 
 // ConvTranspose2d backward-data: dx[n,iy,ix,ci] = sum dy[n, iy*s-pad+ky, ix*s-pad+kx, co] w[ci][ky][kx][co]
 // -- a plain strided conv over dy with the weight in its natural [Cin][KH][KW][Cout] storage.
 static int pdf_deconv2d_bwd_data_impl(const float* dy, const float* w, float* dx,
                                   int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, hipStream_t s, PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};                       // op0: dy, op1: w
+                                  int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
     if (!g_gemm_bf16 && co.ws != nullptr && lddy == Cout && lddx >= Cin) {
         const long need = pdf_internal_x3_deconv_workspace(N, H, W, Cin, Cout, KH, KW, stride, pad, 1);
         if (need > 0 && co.ws_floats >= need && ((uintptr_t)co.ws & 15) == 0) {
-            const CurCall cur(co);
             if (KH != stride || pad != 0) return pdf_internal_x3_deconv_general_bwd_data(dy, w, dx, co.ws, N, H, W, Cin, lddx, Cout, KH, stride, pad, OH, OW, lddy, s);
             return pdf_internal_x3_deconv_bwd_data(dy, w, dx, co.ws, N, H, W, Cin, lddx, Cout, KH, KW, stride, OH, OW, lddy, s);
         }
     }
     IGemm g = {};
-    g.A = dy; g.B = w; g.C = dx; g.bias = nullptr; g.A16 = sh.op0; g.B16 = sh.op1;
+    g.A = dy; g.B = w; g.C = dx; g.bias = nullptr; g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
     g.M = N * H * W; g.N = Cin; g.K = KH * KW * Cout; g.Cin = Cout; g.lda = lddy; g.ldb = KH * KW * Cout; g.ldc = lddx;
     g.H = OH; g.W = OW; g.QH = H; g.QW = W; g.sy = stride; g.sx = stride;
     conv_taps(g, KH, KW, pad, 1);
@@ -2490,28 +2515,31 @@ static int pdf_deconv2d_bwd_data_impl(const float* dy, const float* w, float* dx
 }
 PDF_API int pdf_deconv2d_bwd_data_x(const float* dy, const float* w, float* dx,
                                   int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); }
+                                  int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_deconv2d_bwd_data_impl, dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, stream);
+}
 PDF_API int pdf_deconv2d_bwd_data(const float* dy, const float* w, float* dx,
                                   int N, int H, int W, int Cin, int lddx, int Cout, int KH, int KW,
-                                  int stride, int pad, int OH, int OW, int lddy, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_bwd_data_impl(dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, s, co); pdf_tls_publish(co); return rc; }
+                                  int stride, int pad, int OH, int OW, int lddy, void* stream) {
+    return pdf_call_plain(pdf_deconv2d_bwd_data_impl, dy, w, dx, N, H, W, Cin, lddx, Cout, KH, KW, stride, pad, OH, OW, lddy, stream);
+}
 
 
 // ConvTranspose2d weight gradient in the natural [Cin][KH][KW][Cout] storage.
 static int pdf_deconv2d_bwd_weight_impl(const float* x, const float* dy, float* dw, float* ws, long ws_floats,
                                     int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s, PdfCallOpts& co) {
-    const Shadows sh = {co.op0_bf16, co.op1_bf16};                       // op0: x, op1: dy
+                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
     if (!g_gemm_bf16 && co.ws != nullptr && ldx == Cin && lddy == Cout) {  // x3 form (gemm_x3.hip), workspace in PdfCallOpts::ws
         const long need = pdf_internal_x3_deconv_workspace(N, H, W, Cin, Cout, KH, KW, stride, pad, 2);
         if (need > 0 && co.ws_floats >= need && ((uintptr_t)co.ws & 15) == 0) {
-            const CurCall cur(co);
             if (KH != stride || pad != 0) return pdf_internal_x3_deconv_general_bwd_weight(x, dy, dw, co.ws, N, H, W, Cin, Cout, KH, stride, pad, OH, OW, lddy, accumulate, s);
             return pdf_internal_x3_deconv_bwd_weight(x, dy, dw, co.ws, N, H, W, Cin, Cout, KH, KW, stride, OH, OW, lddy, accumulate, s);
         }
     }
     WGemm g = {};
-    g.P = x; g.Q = dy; g.P16 = sh.op0; g.Q16 = sh.op1; g.M = N * H * W; g.NI = Cin; g.Cq = Cout; g.T = KH * KW;
+    g.P = x; g.Q = dy; g.P16 = co.op0_bf16; g.Q16 = co.op1_bf16; g.M = N * H * W; g.NI = Cin; g.Cq = Cout; g.T = KH * KW;
     g.ldp = ldx; g.ldq = lddy; g.ldw = KH * KW * Cout;
     g.H = OH; g.W = OW; g.QH = H; g.QW = W; g.sy = stride; g.sx = stride; g.plain_q = 0;
     for (int ky = 0; ky < KH; ++ky)
@@ -2523,8 +2551,14 @@ static int pdf_deconv2d_bwd_weight_impl(const float* x, const float* dy, float* 
 }
 PDF_API int pdf_deconv2d_bwd_weight_x(const float* x, const float* dy, float* dw, float* ws, long ws_floats,
                                     int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_deconv2d_bwd_weight_impl(x, dy, dw, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); }
+                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_deconv2d_bwd_weight_impl, x, dy, dw, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy,
+                      accumulate, stream);
+}
 PDF_API int pdf_deconv2d_bwd_weight(const float* x, const float* dy, float* dw, float* ws, long ws_floats,
                                     int N, int H, int W, int Cin, int ldx, int Cout, int KH, int KW,
-                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_deconv2d_bwd_weight_impl(x, dy, dw, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy, accumulate, s, co); pdf_tls_publish(co); return rc; }
+                                    int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream) {
+    return pdf_call_plain(pdf_deconv2d_bwd_weight_impl, x, dy, dw, ws, ws_floats, N, H, W, Cin, ldx, Cout, KH, KW, stride, pad, OH, OW, lddy,
+                          accumulate, stream);
+}
 

@@ -500,7 +500,8 @@ PDF_API long pdf_bn_workspace_floats(int C, long R) {
 static int pdf_bn_train_fwd_impl(const float* x, int ldx, int C, long R, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, float momentum, float eps,
                              const float* res, int ldr, int relu, float* y, int ldy,
-                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, hipStream_t s, PdfCallOpts& co) {
+                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     void* y16 = co.out_bf16;                                 // bf16 shadow of y, vectorised path only
     const TileStats ts = {co.tile_stats, co.tile_n, co.tile_rows};
     const void* x16 = co.bn_x_bf16;
@@ -538,11 +539,17 @@ static int pdf_bn_train_fwd_impl(const float* x, int ldx, int C, long R, const f
 PDF_API int pdf_bn_train_fwd_x(const float* x, int ldx, int C, long R, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, float momentum, float eps,
                              const float* res, int ldr, int relu, float* y, int ldy,
-                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_train_fwd_impl(x, ldx, C, R, gamma, beta, running_mean, running_var, momentum, eps, res, ldr, relu, y, ldy, save_mean, save_rstd, scale, shift, ws, s, co); }
+                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_bn_train_fwd_impl, x, ldx, C, R, gamma, beta, running_mean, running_var, momentum, eps, res, ldr, relu, y, ldy,
+                      save_mean, save_rstd, scale, shift, ws, stream);
+}
 PDF_API int pdf_bn_train_fwd(const float* x, int ldx, int C, long R, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, float momentum, float eps,
                              const float* res, int ldr, int relu, float* y, int ldy,
-                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_train_fwd_impl(x, ldx, C, R, gamma, beta, running_mean, running_var, momentum, eps, res, ldr, relu, y, ldy, save_mean, save_rstd, scale, shift, ws, s, co); pdf_tls_publish(co); return rc; }
+                             float* save_mean, float* save_rstd, float* scale, float* shift, float* ws, void* stream) {
+    return pdf_call_plain(pdf_bn_train_fwd_impl, x, ldx, C, R, gamma, beta, running_mean, running_var, momentum, eps, res, ldr, relu, y, ldy,
+                          save_mean, save_rstd, scale, shift, ws, stream);
+}
 
 
 PDF_API int pdf_bn_eval_fwd(const float* x, int ldx, int C, long R, const float* gamma, const float* beta,
@@ -624,7 +631,8 @@ static int pdf_bn_train_bwd_impl(const float* dy, int lddy, const float* y, int 
                              const float* save_mean, const float* save_rstd, const float* gamma,
                              const float* scale, const float* shift, int C, long R,
                              float* dx, int lddx, float* dres, int lddr, float* dgamma, float* dbeta, int accumulate,
-                             float* ws, hipStream_t s, PdfCallOpts& co) {
+                             float* ws, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     void* dx16 = co.out_bf16;                                  // bf16 shadow of dx
     const void* x16 = co.bn_x_bf16;                         // bf16 storage mode: x comes as bf16; dx == NULL: only the bf16 gradient is written
     if (R <= 0 || C <= 0) return 0;
@@ -675,12 +683,18 @@ PDF_API int pdf_bn_train_bwd_x(const float* dy, int lddy, const float* y, int ld
                              const float* save_mean, const float* save_rstd, const float* gamma,
                              const float* scale, const float* shift, int C, long R,
                              float* dx, int lddx, float* dres, int lddr, float* dgamma, float* dbeta, int accumulate,
-                             float* ws, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_train_bwd_impl(dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, gamma, scale, shift, C, R, dx, lddx, dres, lddr, dgamma, dbeta, accumulate, ws, s, co); }
+                             float* ws, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_bn_train_bwd_impl, dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, gamma, scale, shift, C, R, dx, lddx, dres,
+                      lddr, dgamma, dbeta, accumulate, ws, stream);
+}
 PDF_API int pdf_bn_train_bwd(const float* dy, int lddy, const float* y, int ldy, int relu, const float* x, int ldx,
                              const float* save_mean, const float* save_rstd, const float* gamma,
                              const float* scale, const float* shift, int C, long R,
                              float* dx, int lddx, float* dres, int lddr, float* dgamma, float* dbeta, int accumulate,
-                             float* ws, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_train_bwd_impl(dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, gamma, scale, shift, C, R, dx, lddx, dres, lddr, dgamma, dbeta, accumulate, ws, s, co); pdf_tls_publish(co); return rc; }
+                             float* ws, void* stream) {
+    return pdf_call_plain(pdf_bn_train_bwd_impl, dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, gamma, scale, shift, C, R, dx, lddx, dres,
+                          lddr, dgamma, dbeta, accumulate, ws, stream);
+}
 
 
 // ---------------------------------------------------------------------------------------------
@@ -784,7 +798,8 @@ __global__ __launch_bounds__(256) void bn_maxk_bwd_apply_kernel(const float* __r
 static int pdf_bn_relu_maxk_fwd_impl(const float* y, int ldy, int C, long R, int K, const float* gamma, const float* beta,
                                  float* running_mean, float* running_var, float momentum, float eps, int training,
                                  float* out, int ldo, int* arg, float* save_mean, float* save_rstd, float* scale, float* shift,
-                                 float* ws, hipStream_t s, PdfCallOpts& co) {
+                                 float* ws, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     if (R <= 0 || C <= 0 || K <= 0) return 0;
     if (!v4_ok(C, {ldy, ldo}, {y, out, arg, scale, shift})) return PDF_E_BADARG;
     const long rows = R * K;
@@ -814,11 +829,17 @@ static int pdf_bn_relu_maxk_fwd_impl(const float* y, int ldy, int C, long R, int
 PDF_API int pdf_bn_relu_maxk_fwd_x(const float* y, int ldy, int C, long R, int K, const float* gamma, const float* beta,
                                  float* running_mean, float* running_var, float momentum, float eps, int training,
                                  float* out, int ldo, int* arg, float* save_mean, float* save_rstd, float* scale, float* shift,
-                                 float* ws, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_bn_relu_maxk_fwd_impl(y, ldy, C, R, K, gamma, beta, running_mean, running_var, momentum, eps, training, out, ldo, arg, save_mean, save_rstd, scale, shift, ws, s, co); }
+                                 float* ws, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_bn_relu_maxk_fwd_impl, y, ldy, C, R, K, gamma, beta, running_mean, running_var, momentum, eps, training, out, ldo,
+                      arg, save_mean, save_rstd, scale, shift, ws, stream);
+}
 PDF_API int pdf_bn_relu_maxk_fwd(const float* y, int ldy, int C, long R, int K, const float* gamma, const float* beta,
                                  float* running_mean, float* running_var, float momentum, float eps, int training,
                                  float* out, int ldo, int* arg, float* save_mean, float* save_rstd, float* scale, float* shift,
-                                 float* ws, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_bn_relu_maxk_fwd_impl(y, ldy, C, R, K, gamma, beta, running_mean, running_var, momentum, eps, training, out, ldo, arg, save_mean, save_rstd, scale, shift, ws, s, co); pdf_tls_publish(co); return rc; }
+                                 float* ws, void* stream) {
+    return pdf_call_plain(pdf_bn_relu_maxk_fwd_impl, y, ldy, C, R, K, gamma, beta, running_mean, running_var, momentum, eps, training, out, ldo, arg,
+                          save_mean, save_rstd, scale, shift, ws, stream);
+}
 
 // ws: pdf_bn_workspace_floats(C, R) + 3*C floats
 PDF_API int pdf_bn_relu_maxk_bwd(const float* dout, int lddo, const int* arg, const float* y, int ldy, const float* save_mean, const float* save_rstd,
@@ -1313,7 +1334,8 @@ static int l2_parts(L2Parts& p, int nparts, const float* const* x, const float* 
 }
 // x[i]: [R][C[i]] contiguous rows; y: [R][ldy] with part i at channel offset C[0] + ... + C[i-1]; norm[i]: [R]
 static int pdf_l2norm_cat_fwd_impl(int nparts, const float* const* x, const int* C, const float* const* w, float eps, long R,
-                               float* y, int ldy, float* const* norm, hipStream_t s, PdfCallOpts& co) {
+                               float* y, int ldy, float* const* norm, void* stream, PdfCallOpts& co) {
+    hipStream_t s = (hipStream_t)stream;
     void* y16 = co.out_bf16;                                 // bf16 shadow of y (needs even channel counts)
     if (R <= 0) return 0;
     L2Parts p = {};
@@ -1330,9 +1352,13 @@ static int pdf_l2norm_cat_fwd_impl(int nparts, const float* const* x, const int*
     return 0;
 }
 PDF_API int pdf_l2norm_cat_fwd_x(int nparts, const float* const* x, const int* C, const float* const* w, float eps, long R,
-                               float* y, int ldy, float* const* norm, void* stream, PdfCallOpts* opts) { hipStream_t s = (hipStream_t)stream; PdfCallOpts z = {}; PdfCallOpts& co = opts ? *opts : z; co.stats_tiles = co.stats_rows = 0; return pdf_l2norm_cat_fwd_impl(nparts, x, C, w, eps, R, y, ldy, norm, s, co); }
+                               float* y, int ldy, float* const* norm, void* stream, PdfCallOpts* opts) {
+    return pdf_call_x(opts, pdf_l2norm_cat_fwd_impl, nparts, x, C, w, eps, R, y, ldy, norm, stream);
+}
 PDF_API int pdf_l2norm_cat_fwd(int nparts, const float* const* x, const int* C, const float* const* w, float eps, long R,
-                               float* y, int ldy, float* const* norm, void* stream) { hipStream_t s = (hipStream_t)stream; PdfCallOpts co = pdf_tls_take_all(); const int rc = pdf_l2norm_cat_fwd_impl(nparts, x, C, w, eps, R, y, ldy, norm, s, co); pdf_tls_publish(co); return rc; }
+                               float* y, int ldy, float* const* norm, void* stream) {
+    return pdf_call_plain(pdf_l2norm_cat_fwd_impl, nparts, x, C, w, eps, R, y, ldy, norm, stream);
+}
 
 // dw[i] must be zero-filled (atomically accumulated)
 PDF_API int pdf_l2norm_cat_bwd(int nparts, const float* dy, int lddy, const float* const* x, const int* C, const float* const* w, float eps, long R,

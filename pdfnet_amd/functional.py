@@ -206,7 +206,8 @@ def _stored16(t):
 def _O(**kw):
     """The explicit per-call options of an `_x` entry point (include/pdfnet_hip.h PdfCallOpts): -> (structure, argument).  Every field a
     call takes beyond its positional arguments -- bf16 shadows of its operands, a bf16 output, a statistics request, an operand
-    transform -- is in ITS argument list; nothing is armed on the thread for "the next call"."""
+    transform -- is in ITS argument list; nothing is armed on the thread for "the next call".  This module calls no plain options-taking entry point: every
+    such launch goes through the `_x` form, with None (NULL: no options) where it has none to pass, as the paired linears do."""
     o = None
     for k, v in kw.items():                                  # (the common case -- fp32 mode, no statistics -- allocates nothing)
         if v is not None:
@@ -290,18 +291,6 @@ def share_winograd_input(x):
     if WINOGRAD_SHARE and x is not None and getattr(x, '_pdf_wino_share', None) is None:
         x._pdf_wino_share = {}
     return x
-
-
-def _O2(a, b):
-    """_O2(a, b) for the most frequent call shape: the two operand shadows of a GEMM-family launch."""
-    if a is None and b is None:
-        return None
-    o = _CallOpts()
-    if a is not None:
-        o.op0_bf16 = a.data_ptr()
-    if b is not None:
-        o.op1_bf16 = b.data_ptr()
-    return _byref(o)
 
 
 # ---- BatchNorm statistics out of the producing GEMM's epilogue (fp32 and bf16 kernels): a conv / linear forward called with stats=True
@@ -897,7 +886,7 @@ class _LinearPair(Function):
         M = x.numel() // K // 2
         Nn = w0.shape[0]
         y = torch.empty(x.shape[:-1] + (Nn,), dtype=torch.float32, device=x.device)
-        _L().pdf_linear_fwd_pair(ptr(x), ptr(w0), ptr(w1), ptr(b0), ptr(b1), ptr(y), M, Nn, K, K, K, Nn, act, stream())
+        _L().pdf_linear_fwd_pair_x(ptr(x), ptr(w0), ptr(w1), ptr(b0), ptr(b1), ptr(y), M, Nn, K, K, K, Nn, act, stream(), None)
         ctx.save_for_backward(x, w0, w1, y if act else None)
         ctx.cfg = (act, b0 is not None)
         ctx.params = (w0_in, b0, w1_in, b1)
@@ -917,7 +906,7 @@ class _LinearPair(Function):
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            L.pdf_linear_bwd_data_pair(ptr(g), ptr(w0), ptr(w1), ptr(dx), M, Nn, K, Nn, K, K, stream())
+            L.pdf_linear_bwd_data_pair_x(ptr(g), ptr(w0), ptr(w1), ptr(dx), M, Nn, K, Nn, K, K, stream(), None)
         w0_par, b0_par, w1_par, b1_par = ctx.params
         need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[3]
         need_b = has_b and (ctx.needs_input_grad[2] or ctx.needs_input_grad[4])
@@ -928,7 +917,7 @@ class _LinearPair(Function):
 
         def launch_w(o0, o1, p0, p1, acc):
             n = 2 * L.pdf_wgrad_workspace_floats(M, Nn, K)
-            L.pdf_linear_bwd_weight_pair(ptr(x), ptr(g), ptr(o0), ptr(o1), ptr(p0), ptr(p1), ptr(_ws(n, x.device)), n, M, Nn, K, K, Nn, acc, stream())
+            L.pdf_linear_bwd_weight_pair_x(ptr(x), ptr(g), ptr(o0), ptr(o1), ptr(p0), ptr(p1), ptr(_ws(n, x.device)), n, M, Nn, K, K, Nn, acc, stream(), None)
 
         def launch_b(o0, o1, acc):
             ws = _ws(2 * _bn_ws_floats(Nn, M), x.device)

@@ -306,6 +306,28 @@ def test_rejected_call_leaves_no_armed_slot():
     assert rc == -1 and o.stats_tiles == 0 and L.pdf_debug_armed_slots() == 8      # (an `_x` call does not touch the compat slots)
     c.pdf_linear_fwd_pair(None, None, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, None)                 # any plain GEMM-family call clears them
     assert L.pdf_debug_armed_slots() == 0
+    # Both conventions for EVERY options-taking entry point (the library keeps each in one helper, csrc/common.h pdf_call_plain / pdf_call_x).
+    # The argument lists come from the header's prototypes; all-NULL / zero-size arguments make every one of them return before any launch:
+    # 0 (empty problem) or PDF_E_BADARG -- a positive code would be a hipError_t, i.e. a launch attempted on this GPU-less machine.
+    names = sorted(n[:-2] for n in L.protos if n.endswith('_x') and n[:-2] in L.protos)
+    assert len(names) == 17, names
+    zero = {ctypes.c_void_p: None, ctypes.c_int: 0, ctypes.c_long: 0, ctypes.c_float: 0.0}
+    for n in names:
+        assert L.protos[n + '_x'] == (ctypes.c_int, L.protos[n][1] + [ctypes.c_void_p]), n      # same arguments, then PdfCallOpts*
+        args = [zero[t] for t in L.protos[n][1]]
+        arm()
+        rc = getattr(c, n)(*args)                                # plain: takes and clears every slot, whatever it returns
+        assert rc in (0, -1) and L.pdf_debug_armed_slots() == 0, (n, rc)
+        assert L.pdf_stats_result_tiles() == 0 and L.pdf_stats_result_rows() == 0, n
+        arm()
+        o = hip.CallOpts(stats_out=0x5000, stats_cap=64, stats_tiles=7, stats_rows=9)
+        rc = getattr(c, n + '_x')(*args, ctypes.byref(o))        # explicit: zeroes the OUT fields first thing, leaves the thread's slots alone
+        assert rc in (0, -1) and (o.stats_tiles, o.stats_rows) == (0, 0) and L.pdf_debug_armed_slots() == 8, (n, rc, o.stats_tiles, o.stats_rows)
+        assert (o.stats_out, o.stats_cap) == (0x5000, 64), n     # (the request itself is the caller's: not cleared)
+        rc = getattr(c, n + '_x')(*args, None)                   # NULL options = an all-zero block
+        assert rc in (0, -1) and L.pdf_debug_armed_slots() == 8, (n, rc)
+    c.pdf_linear_fwd_pair(None, None, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, None)
+    assert L.pdf_debug_armed_slots() == 0
 
 
 def test_bf16_storage_defaults_to_the_batches_where_it_wins(monkeypatch):

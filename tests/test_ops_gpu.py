@@ -1053,6 +1053,40 @@ def test_plain_c_client_of_the_c_abi(F, tmp_path):
     assert "c_client: ok" in r.stdout, r.stdout
 
 
+def test_plain_form_publishes_the_statistics_layout(F):
+    """The compat channel end to end on a launch that succeeds: pdf_set_stats_output, a plain pdf_linear_fwd, then pdf_stats_result_tiles /
+    _rows report the layout the launch chose -- the same one the `_x` form writes into its PdfCallOpts -- and the partials hold the per-block
+    column means.  The next plain call, which asks for nothing, reports 0 again."""
+    import ctypes
+    from pdfnet_amd import hip
+    L = hip.lib()
+    M, N, K = 256, 64, 64
+    x, w = rnd(M, K, seed=1).cuda(), rnd(N, K, seed=2).cuda()
+    y, y2 = torch.empty(M, N, device='cuda'), torch.empty(M, N, device='cuda')
+    part, part2 = torch.zeros(4096, device='cuda'), torch.zeros(4096, device='cuda')
+    prec = L.pdf_debug_gemm_precision()
+    L.pdf_set_gemm_precision(0)
+    try:
+        L.pdf_set_stats_output(part.data_ptr(), part.numel())
+        L.pdf_linear_fwd(x.data_ptr(), w.data_ptr(), None, y.data_ptr(), M, N, K, K, K, N, 0, hip.stream())
+        tiles, rows = L.pdf_stats_result_tiles(), L.pdf_stats_result_rows()
+        assert L.pdf_debug_armed_slots() == 0
+        o = hip.CallOpts(stats_out=part2.data_ptr(), stats_cap=part2.numel())
+        L.pdf_linear_fwd_x(x.data_ptr(), w.data_ptr(), None, y2.data_ptr(), M, N, K, K, K, N, 0, hip.stream(), ctypes.byref(o))
+        L.pdf_linear_fwd(x.data_ptr(), w.data_ptr(), None, y2.data_ptr(), M, N, K, K, K, N, 0, hip.stream())
+        after = (L.pdf_stats_result_tiles(), L.pdf_stats_result_rows())
+    finally:
+        L.pdf_set_gemm_precision(prec)
+    torch.cuda.synchronize()
+    assert tiles > 0 and rows > 0 and (tiles - 1) * rows < M <= tiles * rows, (tiles, rows)
+    assert (o.stats_tiles, o.stats_rows) == (tiles, rows) and after == (0, 0)
+    assert torch.equal(part, part2) and torch.equal(y, y2)
+    mean = part[:tiles * N * 2].view(tiles, N, 2)[..., 0]
+    want = y.view(tiles, rows, N).mean(1)                      # (M is a whole number of row blocks here)
+    # both are fp32 means of `rows` <= 128 values no larger than max|y|: each side is within rows * 2^-24 * max|y| of the exact mean
+    assert (mean - want).abs().max().item() <= 2 * rows * 2.0 ** -24 * y.abs().max().item()
+
+
 def test_gradient_chain_of_a_map_with_several_consumers(F):
     """max pool (skip) -> row gather (chain) -> row gather (chain) -> window gather (chain) on ONE feature map: the backward
     passes fill one gradient tensor; the result equals the sum autograd forms from independent consumers."""
