@@ -100,6 +100,15 @@ static int attn_group(int V, int dh) {                 // lanes per row: power o
     while (G < 16 && G < dh && V * G * 2 <= 1024) G <<= 1;
     return G;
 }
+// Which split a launch takes (see the *_keys kernels below).  The forward and the two backward launches of one attention decide alike: the
+// *_keys family is taken only when all of its kernels fit their staging in 64 KB of LDS (the largest are the two backward ones), so that a
+// shape the forward accepts is never refused by its backward (V = 300 at dh = 16 was: 65.3 KB in attn_bwd_q_keys_kernel).
+static bool attn_keys_split(int V, int dh, int G) {
+    if (dh > 32 || G <= 1) return false;
+    const size_t RPB = 256 / G, LD = dh + 1;
+    const size_t smem_q = (2 * (size_t)V + 3 * RPB) * LD, smem_kv = (2 * (size_t)V + 2 * RPB) * LD + 3 * (size_t)V;
+    return (smem_q > smem_kv ? smem_q : smem_kv) * sizeof(float) <= 64 * 1024;
+}
 
 template <int DH, int G>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ld,
@@ -371,7 +380,7 @@ PDF_API int pdf_attn_fwd(const float* q, const float* k, const float* v, int ld,
     hipStream_t s = (hipStream_t)stream;
     if (V <= 0) return PDF_E_BADARG;
     const int G = attn_group(V, dh), NT = cdiv(V, 256 / G);
-    const bool keys = dh <= 32 && G > 1;                   // which split (see the *_keys kernels)
+    const bool keys = attn_keys_split(V, dh, G);
     size_t smem = keys ? (size_t)(2 * V + 256 / G) * (dh + 1) * sizeof(float) : (size_t)2 * V * dh * sizeof(float);
     if (smem > 64 * 1024) return PDF_E_BADARG;
     float inv_norm = 1.f / sqrtf((float)dh);
@@ -512,7 +521,7 @@ PDF_API int pdf_attn_bwd(const float* q, const float* k, const float* v, int ld,
     hipStream_t s = (hipStream_t)stream;
     if (V <= 0) return PDF_E_BADARG;
     const int G = attn_group(V, dh), NT = cdiv(V, 256 / G), RPB = 256 / G;
-    const bool keys = dh <= 32 && G > 1;
+    const bool keys = attn_keys_split(V, dh, G);
     const size_t smem_q = keys ? (size_t)(2 * V + 3 * RPB) * (dh + 1) * sizeof(float) : (size_t)2 * V * dh * sizeof(float);
     const size_t smem_kv = keys ? ((size_t)(2 * V + 2 * RPB) * (dh + 1) + 3 * V) * sizeof(float) : (size_t)(2 * V * dh + 3 * V) * sizeof(float);
     if (smem_q > 64 * 1024 || smem_kv > 64 * 1024) return PDF_E_BADARG;

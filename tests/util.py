@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (test infrastructure; may import oracle/)."""
+import contextlib
 import os
 import types
 
@@ -171,3 +172,91 @@ def build_c_client(out_dir):
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     return exe
+
+
+# ----------------------------------------------------------------------------------------------
+# Dropout: pin the seed a site draws, and recover the keep-mask a kernel used from the kernel itself (tests/test_dropout_gpu.py).
+# The masks are counter-based -- a pure function of (host seed, device step counter, element index) -- so a probe with the same seed and
+# step on inputs made of zeros and ones reads the mask back without restating the hash.
+@contextlib.contextmanager
+def pinned_seeds(F, seeds, step=0):
+    """While active, F.next_seed() hands out `seeds` in order (every dropout site calls the module-level function) and the device step
+    counter holds `step`.  -> namespace with .seeds and .drawn (how many were taken; one more than there are is an error).
+    F._seed_state[0], the step counter's value and F.next_seed itself are put back on exit."""
+    counter = F.step_counter(torch.device('cuda', torch.cuda.current_device()))
+    saved_state, saved_step, saved_fn = F._seed_state[0], int(counter.item()), F.next_seed
+    pin = types.SimpleNamespace(seeds=[int(s) for s in seeds], drawn=0)
+
+    def draw():
+        assert pin.drawn < len(pin.seeds), "a dropout site drew seed number %d of %d pinned ones" % (pin.drawn + 1, len(pin.seeds))
+        pin.drawn += 1
+        return pin.seeds[pin.drawn - 1]
+    F.next_seed = draw
+    counter.fill_(int(step))
+    try:
+        yield pin
+    finally:
+        torch.cuda.synchronize()
+        F.next_seed = saved_fn
+        F._seed_state[0] = saved_state
+        counter.fill_(saved_step)
+
+
+@contextlib.contextmanager
+def recorded_seeds(F):
+    """While active, every seed F.next_seed() hands out is appended to the list this yields (the seeds themselves are unchanged)."""
+    saved_fn, log = F.next_seed, []
+
+    def draw():
+        log.append(saved_fn())
+        return log[-1]
+    F.next_seed = draw
+    try:
+        yield log
+    finally:
+        F.next_seed = saved_fn
+
+
+def probe_dropout_mask(F, shape, p, seed, step=0):
+    """Keep-mask of F.dropout at `shape` (bool, CPU): dropout(ones) > 0."""
+    with pinned_seeds(F, [seed], step):
+        y = F.dropout(torch.ones(shape, device='cuda'), p, True)
+        return (y > 0).cpu()
+
+
+def probe_dropout_add_mask(F, shape, p, seed, step=0):
+    """Keep-mask of F.dropout_add at `shape`: dropout_add(ones, zeros) > 0."""
+    with pinned_seeds(F, [seed], step):
+        y = F.dropout_add(torch.ones(shape, device='cuda'), torch.zeros(shape, device='cuda'), p, True)
+        return (y > 0).cpu()
+
+
+def probe_ln_fused_mask(F, shape, p, seed, step=0):
+    """Keep-mask of the fused-LayerNorm site on x [2, ..., Fd] with paired parameters: x = 0 is the residual, add = 1 the dropped operand,
+    so the returned residual stream z is mask / (1 - p)."""
+    Fd = shape[-1]
+    one, zero = torch.ones(Fd, device='cuda'), torch.zeros(Fd, device='cuda')
+    with pinned_seeds(F, [seed], step):
+        z, _ = F.layer_norm_fused(torch.zeros(shape, device='cuda'), one, zero, 1e-6, F.ACT_NONE, add=torch.ones(shape, device='cuda'), p=p,
+                                  training=True, gamma1=one, beta1=zero)
+        return (z > 0).cpu()
+
+
+def probe_attention_mask(F, nb, V, Fd, heads, p, seed, step=0, kv_shift=0):
+    """Keep-mask of F.attention's probabilities, [nb, heads, V (query), V (key)] bool on the CPU.  q = k = 0 makes every probability 1 / V;
+    v[b, j, h * dh + c] = 1 iff j == base + c turns output feature c of head h into (mask of key base + c) / ((1 - p) V); base walks over
+    the keys in ceil(V / dh) calls with the same seed."""
+    dh = Fd // heads
+    q = torch.zeros(nb, V, Fd, device='cuda')
+    mask = torch.zeros(nb, heads, V, V, dtype=torch.bool)
+    calls = (V + dh - 1) // dh
+    with pinned_seeds(F, [seed] * calls, step) as pin:
+        for base in range(0, V, dh):
+            n = min(dh, V - base)
+            v = torch.zeros(nb, V, heads, dh)
+            for c in range(n):
+                v[:, base + c, :, c] = 1
+            out = F.attention(q, q, v.reshape(nb, V, Fd).cuda(), heads, p, True, kv_shift)
+            mask[:, :, :, base:base + n] = (out.reshape(nb, V, heads, dh)[..., :n] > 0).permute(0, 2, 1, 3).cpu()
+        assert pin.drawn == calls
+    return mask
