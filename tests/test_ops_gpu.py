@@ -1,5 +1,6 @@
 """GPU parity of every C-ABI kernel (called through pdfnet_amd.functional -> ctypes -> libpdfnet_hip.so)
-against a plain PyTorch fp32 CPU reference of the same op (or the oracle for the point / MANO ops)."""
+against a plain PyTorch fp32 CPU reference of the same op (or the oracle for the point / MANO ops).
+Which kernel a GEMM-family shape runs is asserted in tests/test_gemm_dispatch_gpu.py, not here."""
 import numpy as np
 import pytest
 import torch
@@ -67,16 +68,19 @@ CONVS = [  # N, Cin, H, W, Cout, k, stride, pad, act, bias
     (4, 1024, 16, 16, 256, 3, 1, 1, 0, False),
     # streaming kernels for tiny channel counts: e_conv1 (3 -> 3, full resolution), the 2-channel hm / mask heads
     (2, 3, 192, 200, 3, 3, 1, 1, 1, False), (2, 256, 64, 64, 2, 1, 1, 0, 0, True), (2, 128, 128, 128, 2, 1, 1, 0, 0, True),
-    # >= 600 128x128 tiles of a 3x3 stride-1 conv with >= 256 input channels: the LDS-halo kernel, W = 64 / 32 / 16 (no ReLU here: with 10 M
-    # outputs a few pre-activations sit within rounding of 0 and flip the mask between implementations)
+    # wide 3x3 stride-1 layers on 64 / 32 / 16-wide maps.  This test asks for gradients, so with Winograd on (the default) all three launches
+    # of each are F(4x4) Winograd ones, x3 products (T = 1280 tiles); the LDS-halo kernel these shapes select with Winograd off, or
+    # in a forward without gradients, is pinned in tests/test_gemm_dispatch_gpu.py (no ReLU here: with 10 M outputs a few pre-activations
+    # sit within rounding of 0 and flip the mask between implementations)
     (5, 256, 64, 64, 512, 3, 1, 1, 0, True), (5, 512, 64, 64, 256, 3, 1, 1, 0, False), (20, 272, 32, 32, 512, 3, 1, 1, 0, False),
     (20, 512, 32, 32, 256, 3, 1, 1, 0, True), (80, 256, 16, 16, 512, 3, 1, 1, 0, True), (80, 512, 16, 16, 256, 3, 1, 1, 0, False),
     # valid 3x3 on the 5x5 / 3x3 centre windows (few rows, long reduction: 32x32 tiles)
     (64, 256, 5, 5, 512, 3, 1, 0, 0, False), (64, 512, 3, 3, 1024, 3, 1, 0, 0, False),
     # the ResNet stem at output widths that are multiples of 64: its dedicated MFMA weight-gradient kernel (image borders on all sides)
     (3, 3, 128, 128, 64, 7, 2, 3, 0, False), (2, 3, 64, 256, 64, 7, 2, 3, 1, False),
-    # the LDS-DMA weight-gradient kernel's issue paths: scalar offsets (16-pixel K-steps: stride 2, a 48-wide map that wraps every
-    # third step, plain 1x1 rows) and the per-row form (a 40-wide map)
+    # the LDS-DMA weight-gradient kernel (wgemm_tn_dma<3, true>), scalar-offset form: stride 2 and plain 1x1 rows.  The 48-wide (T = 1728
+    # tiles) and the 40-wide map (T = 1600) are F(4x4) Winograd launches here, whose batched weight-gradient product is the same kernel on
+    # plain rows; the wrapping scalar-offset form and the per-row form of the direct weight gradient are pinned in tests/test_gemm_dispatch_gpu.py
     (24, 128, 64, 64, 256, 3, 2, 1, 0, False), (12, 128, 48, 48, 256, 3, 1, 1, 0, False), (24, 256, 32, 32, 512, 1, 1, 0, 0, True),
     (16, 128, 40, 40, 256, 3, 1, 1, 0, False)]
 
@@ -1195,6 +1199,10 @@ def test_batchnorm_statistics_from_the_gemm_epilogue(F, cfg, monkeypatch):
         res[mode] = (out.detach(), rm, rv, xd.grad, wd.grad, gd.grad, bd.grad, y.detach())
     for a, c, what in zip(res['epilogue'], res['pass'], ('out', 'running_mean', 'running_var', 'dx', 'dw', 'dgamma', 'dbeta', 'y')):
         close(a, c.cpu(), 2e-5, rtol=2e-5, what=what)
+    # the convolution itself against float64 (test_conv2d's bar): the wide direct kernels this test reaches with Winograd off are not
+    # compared with themselves only
+    ref = TF.conv2d(x.double(), w.double(), None, st, pad)
+    close(res['pass'][7], TF.relu(ref) if act else ref, 3e-5 * max(1, (Cin * k * k) ** 0.5 / 16), what="conv fwd vs float64")
     y64 = res['pass'][7].cpu().double().permute(0, 2, 3, 1).reshape(-1, Cout)
     mean, var = y64.mean(0), y64.var(0, unbiased=True)
     close(res['epilogue'][1], (0.9 * rm0.double() + 0.1 * mean).float(), 1e-5, rtol=1e-5, what="running_mean vs float64")

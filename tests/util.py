@@ -260,3 +260,29 @@ def probe_attention_mask(F, nb, V, Fd, heads, p, seed, step=0, kv_shift=0):
             mask[:, :, :, base:base + n] = (out.reshape(nb, V, heads, dh)[..., :n] > 0).permute(0, 2, 1, 3).cpu()
         assert pin.drawn == calls
     return mask
+
+
+# ----------------------------------------------------------------------------------------------
+# Which kernels ran: the library's per-kernel records (pdf_debug_kernel_timing / _record; the names are the strings the sources give to
+# KTimer).  tests/test_gemm_dispatch_gpu.py pins the kernel every parity case is meant for with it.
+@contextlib.contextmanager
+def kernels_run(F):
+    """Yields a list that, on leaving the block, holds the recorded kernel symbol of every GEMM-family launch issued inside it, in launch
+    order (deferred weight gradients are flushed and the device is idle before the records are read).  Recording is switched off on exit,
+    also when the block raises.  The Winograd transforms carry no record: whether a launch took the Winograd path is what
+    pdf_conv2d_winograd_workspace_floats says about it."""
+    import ctypes
+    L = F._L()
+    names = []
+    assert L.pdf_debug_kernel_timing(1) == 0
+    try:
+        yield names
+        F.join_wgrad()
+        torch.cuda.synchronize()
+        nm = ctypes.create_string_buffer(128)
+        fl, by, ms = ctypes.c_double(), ctypes.c_double(), ctypes.c_float()
+        for i in range(L.pdf_debug_kernel_record_count()):
+            assert L.pdf_debug_kernel_record(i, nm, 128, ctypes.byref(fl), ctypes.byref(by), ctypes.byref(ms)) == 0
+            names.append(nm.value.decode())
+    finally:
+        L.pdf_debug_kernel_timing(0)
