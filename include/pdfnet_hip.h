@@ -221,6 +221,24 @@ int pdf_bn_train_bwd(const float* dy, int lddy, const float* y, int ldy, int rel
                      const float* scale, const float* shift, int C, long R,
                      float* dx, int lddx, float* dres, int lddr, float* dgamma, float* dbeta, int accumulate,
                      float* ws, void* stream);
+/* BatchNorm with FROZEN statistics (forward: pdf_bn_eval_fwd), backward -- nn.BatchNorm2d/1d in eval mode under autograd.
+ *   g = dy * mask;  dx = g * scale;  dres = g;
+ *   dbeta (+)= sum_r g;  dgamma (+)= sum_r g * (x - running_mean) * rsqrt(running_var + eps)
+ * relu: 0 none; 1 mask from the saved output y; 2 no residual, mask recomputed from x as fmaf(x, scale, shift) > 0
+ * (the expression of the forward: the mask must be the forward's).  scale / shift: what pdf_bn_eval_fwd wrote.
+ * dgamma == dbeta == NULL: no sums, no second launch, x is read only for relu == 2.  dx == NULL: sums only.
+ * accumulate as in pdf_bn_train_bwd.  ws >= pdf_bn_workspace_floats(C, R) when sums are asked for.  One pass over the
+ * tensors, no atomics: two runs are bit-identical. */
+int pdf_bn_eval_bwd(const float* dy, int lddy, const float* y, int ldy, int relu, const float* x, int ldx,
+                    const float* running_mean, const float* running_var, float eps, const float* scale, const float* shift,
+                    int C, long R, float* dx, int lddx, float* dres, int lddr,
+                    float* dgamma, float* dbeta, int accumulate, float* ws, void* stream);
+/* the same for the set-abstraction tail (forward: pdf_bn_relu_maxk_fwd with training == 0): dy[r][k][c] = dout[r][c] * scale[c]
+ * where k == arg[r][c] and the ReLU was active, else 0; the sums run over the R*C selected elements only.  C % 4 == 0.
+ * dgamma == dbeta == NULL: no sums.  dy == NULL: sums only.  ws >= pdf_bn_workspace_floats(C, R) when sums are asked for. */
+int pdf_bn_relu_maxk_eval_bwd(const float* dout, int lddo, const int* arg, const float* y, int ldy,
+                              const float* running_mean, const float* running_var, float eps, const float* scale, const float* shift,
+                              int C, long R, int K, float* dy, int lddy, float* dgamma, float* dbeta, int accumulate, float* ws, void* stream);
 /* out[c] (+)= sum_r g[r][c] (bias gradients); ws >= pdf_bn_workspace_floats(C,R) */
 int pdf_colsum(const float* g, int ldg, int C, long R, float* out, int accumulate, float* ws, void* stream);
 /* paired: rows [0, R) -> out0, rows [R, 2R) -> out1; ws >= 2 * pdf_bn_workspace_floats(C,R) */

@@ -696,6 +696,148 @@ PDF_API int pdf_bn_train_bwd(const float* dy, int lddy, const float* y, int ldy,
                           lddr, dgamma, dbeta, accumulate, ws, stream);
 }
 
+// ---- backward with FROZEN statistics (forward: pdf_bn_eval_fwd).  The statistics do not depend on x, so no mean term reaches dx:
+//   g = dy * mask;  dx = g * scale;  dres = g;  dbeta = sum g;  dgamma = sum g * xhat,  xhat = (x - running_mean) * rsqrt(running_var + eps)
+// ONE streaming pass (dy, x -> dx; y / dres with a residual) where the training backward makes two over (dy, x); the per-chunk sums
+// it leaves in `part` are finished by bn_eval_bwd_finalize_kernel.  xhat comes from the running statistics, never from
+// (y - beta) / gamma: a channel with gamma == 0 still has a dgamma.  SUMS == false (neither parameter wants a gradient): purely
+// element-wise -- no partials, no LDS, no second launch, and x is read only to recompute the mask (relu == 2).
+template <bool SUMS>
+__global__ __launch_bounds__(256) void bn_eval_bwd_v4_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int relu,
+                                                             const float* __restrict__ x, int ldx, const float* __restrict__ rmean,
+                                                             const float* __restrict__ rvar, float eps, const float* __restrict__ scale,
+                                                             const float* __restrict__ shift, int C, long R, long rows_per_chunk,
+                                                             float* __restrict__ dx, int lddx, float* __restrict__ dres, int lddr,
+                                                             float* __restrict__ part) {
+    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
+    const int c0 = blockIdx.x * BN_CT + tx * 4;
+    long row_s, row_e, row_step;
+    v4_rows(rows_per_chunk, R, ty, row_s, row_e, row_step);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+    if (c0 < C) {
+        float4 m = a, rs = a, sc = a, sh = a;
+        if (SUMS) {
+            m = *reinterpret_cast<const float4*>(rmean + c0);
+            const float4 v = *reinterpret_cast<const float4*>(rvar + c0);
+            rs = make_float4(1.f / sqrtf(v.x + eps), 1.f / sqrtf(v.y + eps), 1.f / sqrtf(v.z + eps), 1.f / sqrtf(v.w + eps));
+        }
+        if (dx != nullptr || relu == 2) sc = *reinterpret_cast<const float4*>(scale + c0);
+        if (relu == 2) sh = *reinterpret_cast<const float4*>(shift + c0);
+        const bool need_x = SUMS || relu == 2;
+#pragma unroll 4
+        for (long r = row_s; r < row_e; r += row_step) {
+            float4 g = *reinterpret_cast<const float4*>(dy + r * lddy + c0);
+            float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (need_x) xv = *reinterpret_cast<const float4*>(x + r * ldx + c0);
+            if (relu) {
+                const float4 yv = relu == 2 ? make_float4(fmaf(xv.x, sc.x, sh.x), fmaf(xv.y, sc.y, sh.y), fmaf(xv.z, sc.z, sh.z), fmaf(xv.w, sc.w, sh.w))
+                                            : *reinterpret_cast<const float4*>(y + r * ldy + c0);
+                if (!(yv.x > 0.f)) g.x = 0.f;
+                if (!(yv.y > 0.f)) g.y = 0.f;
+                if (!(yv.z > 0.f)) g.z = 0.f;
+                if (!(yv.w > 0.f)) g.w = 0.f;
+            }
+            if (dres != nullptr) *reinterpret_cast<float4*>(dres + r * lddr + c0) = g;
+            if (dx != nullptr) *reinterpret_cast<float4*>(dx + r * lddx + c0) = make_float4(g.x * sc.x, g.y * sc.y, g.z * sc.z, g.w * sc.w);
+            if (SUMS) {
+                a.x += g.x; a.y += g.y; a.z += g.z; a.w += g.w;
+                b.x += g.x * (xv.x - m.x) * rs.x; b.y += g.y * (xv.y - m.y) * rs.y;
+                b.z += g.z * (xv.z - m.z) * rs.z; b.w += g.w * (xv.w - m.w) * rs.w;
+            }
+        }
+    }
+    if constexpr (SUMS) {
+        __shared__ float4 sa[V4_TY][V4_TX], sb[V4_TY][V4_TX];
+        v4_block_reduce(a, b, sa, sb, part, C, c0, true);
+    }
+}
+
+// scalar form (C % 4 != 0, an odd leading dimension, an unaligned pointer): 64 channels x 4 row lanes, the layout of
+// bn_bwd_partial_kernel; part == NULL: no sums
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int relu,
+                                                          const float* __restrict__ x, int ldx, const float* __restrict__ rmean,
+                                                          const float* __restrict__ rvar, float eps, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, int C, long R, long rows_per_chunk,
+                                                          float* __restrict__ dx, int lddx, float* __restrict__ dres, int lddr,
+                                                          float* __restrict__ part) {
+    __shared__ float s1[4][BN_CT], s2[4][BN_CT];
+    const int tx = threadIdx.x & (BN_CT - 1), ty = threadIdx.x / BN_CT;
+    const int c = blockIdx.x * BN_CT + tx;
+    const long r0 = blockIdx.y * rows_per_chunk;
+    const long r1 = min(R, r0 + rows_per_chunk);
+    const bool sums = part != nullptr;
+    float a = 0.f, b = 0.f;
+    if (c < C) {
+        const float m = sums ? rmean[c] : 0.f, rs = sums ? 1.f / sqrtf(rvar[c] + eps) : 0.f;
+        const float sc = (dx != nullptr || relu == 2) ? scale[c] : 0.f, sh = relu == 2 ? shift[c] : 0.f;
+        for (long r = r0 + ty; r < r1; r += 4) {
+            float g = dy[r * lddy + c];
+            const float xv = (sums || relu == 2) ? x[r * ldx + c] : 0.f;
+            if (relu && !((relu == 2 ? fmaf(xv, sc, sh) : y[r * ldy + c]) > 0.f)) g = 0.f;
+            if (dres != nullptr) dres[r * lddr + c] = g;
+            if (dx != nullptr) dx[r * lddx + c] = g * sc;
+            a += g; b += g * (xv - m) * rs;
+        }
+    }
+    if (!sums) return;
+    s1[ty][tx] = a; s2[ty][tx] = b;
+    __syncthreads();
+    if (ty == 0 && c < C) {
+        part[((long)blockIdx.y * C + c) * 2 + 0] = s1[0][tx] + s1[1][tx] + s1[2][tx] + s1[3][tx];
+        part[((long)blockIdx.y * C + c) * 2 + 1] = s2[0][tx] + s2[1][tx] + s2[2][tx] + s2[3][tx];
+    }
+}
+
+// the chunk partials (sum g, sum g * xhat) in a fixed order, in double -> dbeta, dgamma (either may be NULL)
+__global__ __launch_bounds__(FIN_TX * FIN_TY) void bn_eval_bwd_finalize_kernel(const float* __restrict__ part, int chunks, int C,
+                                                                               float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
+    __shared__ double s1[FIN_TY][FIN_TX], s2[FIN_TY][FIN_TX];
+    const int c = blockIdx.x * FIN_TX + threadIdx.x;
+    double a, b;
+    reduce_chunks(part, chunks, C, c, threadIdx.y, s1, s2, a, b);
+    if (c >= C || threadIdx.y != 0) return;
+    if (dbeta != nullptr) { if (accumulate) dbeta[c] += (float)a; else dbeta[c] = (float)a; }
+    if (dgamma != nullptr) { if (accumulate) dgamma[c] += (float)b; else dgamma[c] = (float)b; }
+}
+
+PDF_API int pdf_bn_eval_bwd(const float* dy, int lddy, const float* y, int ldy, int relu, const float* x, int ldx,
+                            const float* running_mean, const float* running_var, float eps, const float* scale, const float* shift,
+                            int C, long R, float* dx, int lddx, float* dres, int lddr,
+                            float* dgamma, float* dbeta, int accumulate, float* ws, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (R <= 0 || C <= 0) return 0;
+    const bool sums = dgamma != nullptr || dbeta != nullptr;
+    const bool need_x = sums || relu == 2;
+    if (relu < 0 || relu > 2 || dy == nullptr) return PDF_E_BADARG;
+    if ((relu == 1 && y == nullptr) || (relu == 2 && (scale == nullptr || shift == nullptr || dres != nullptr))) return PDF_E_BADARG;
+    if ((need_x && x == nullptr) || (dx != nullptr && scale == nullptr)) return PDF_E_BADARG;
+    if (sums && (running_mean == nullptr || running_var == nullptr || ws == nullptr)) return PDF_E_BADARG;
+    if (!sums && dx == nullptr && dres == nullptr) return 0;
+    long chunks = bn_chunks(C, R);
+    long rpc = (R + chunks - 1) / chunks;
+    chunks = (R + rpc - 1) / rpc;
+    const bool use_sc = dx != nullptr || relu == 2;
+    const bool vec = v4_ok(C, {lddy, need_x ? ldx : 0, dx ? lddx : 0, relu == 1 ? ldy : 0, dres ? lddr : 0},
+                           {dy, need_x ? x : nullptr, dx, dres, relu == 1 ? y : nullptr, sums ? running_mean : nullptr, sums ? running_var : nullptr,
+                            use_sc ? scale : nullptr, relu == 2 ? shift : nullptr});
+    if (vec && sums)
+        hipLaunchKernelGGL((bn_eval_bwd_v4_kernel<true>), dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dy, lddy, y, ldy, relu, x, ldx,
+                           running_mean, running_var, eps, scale, shift, C, R, rpc, dx, lddx, dres, lddr, ws);
+    else if (vec) {                                          // element-wise: the finer chunks of the streaming passes
+        const long arpc = apply_rows_per_chunk(C, R);
+        hipLaunchKernelGGL((bn_eval_bwd_v4_kernel<false>), dim3(cdiv(C, BN_CT), (unsigned)((R + arpc - 1) / arpc)), dim3(256), 0, s, dy, lddy, y, ldy, relu,
+                           x, ldx, running_mean, running_var, eps, scale, shift, C, R, arpc, dx, lddx, dres, lddr, nullptr);
+    } else
+        hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dy, lddy, y, ldy, relu, x, ldx,
+                           running_mean, running_var, eps, scale, shift, C, R, rpc, dx, lddx, dres, lddr, sums ? ws : nullptr);
+    PDF_LAUNCH_CHECK();
+    if (sums) {
+        hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, C, dgamma, dbeta, accumulate);
+        PDF_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // Set-abstraction tail (intaghand_encoder.py:59-62,79-82,97-100: BatchNorm2d -> ReLU -> MaxPool2d over the K neighbours) in
@@ -861,6 +1003,88 @@ PDF_API int pdf_bn_relu_maxk_bwd(const float* dout, int lddo, const int* arg, co
     hipLaunchKernelGGL(bn_maxk_bwd_apply_kernel, dim3(grid_for(total)), dim3(256), 0, s, dout, lddo, arg, y, ldy, save_mean, save_rstd, coef,
                        scale, shift, C, K, dy, lddy, total);
     PDF_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the same tail with FROZEN statistics (forward: training == 0).  No mean term reaches the rows that lost the max, so their
+// gradient is an exact zero and y is needed only at the R*C selected elements.  Of the two possible shapes -- a zero fill of dy
+// followed by a scatter of the selected elements, or the apply kernel's walk over k -- this is the walk: dy is written exactly
+// once, in whole float4 rows (the scatter would write 4-byte pieces into rows the fill has just streamed out, behind a second
+// launch), and y is still not streamed: each thread gathers its four selected elements before the loop.
+__global__ __launch_bounds__(256) void bn_maxk_eval_bwd_partial_kernel(const float* __restrict__ dm, int lddm, const int* __restrict__ arg,
+                                                                       const float* __restrict__ y, int ldy, const float* __restrict__ rmean,
+                                                                       const float* __restrict__ rvar, float eps, const float* __restrict__ scale,
+                                                                       const float* __restrict__ shift, int C, int K, long R, long rows_per_chunk,
+                                                                       float* __restrict__ part) {
+    __shared__ float4 sa[V4_TY][V4_TX], sb[V4_TY][V4_TX];
+    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
+    const int c0 = blockIdx.x * BN_CT + tx * 4;
+    const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+    if (c0 < C) {
+        const float4 m = *reinterpret_cast<const float4*>(rmean + c0), var = *reinterpret_cast<const float4*>(rvar + c0);
+        const float4 rs = make_float4(1.f / sqrtf(var.x + eps), 1.f / sqrtf(var.y + eps), 1.f / sqrtf(var.z + eps), 1.f / sqrtf(var.w + eps));
+        const float4 sc = *reinterpret_cast<const float4*>(scale + c0), sh = *reinterpret_cast<const float4*>(shift + c0);
+        for (long r = r0 + ty; r < r1; r += V4_TY) {
+            const float4 g4 = *reinterpret_cast<const float4*>(dm + r * lddm + c0);
+            const int4 k4 = *reinterpret_cast<const int4*>(arg + r * C + c0);
+            const float* base = y + r * K * ldy + c0;
+            const float vx = base[(long)k4.x * ldy], vy = base[(long)k4.y * ldy + 1], vz = base[(long)k4.z * ldy + 2], vw = base[(long)k4.w * ldy + 3];
+            const float gx = fmaf(vx, sc.x, sh.x) > 0.f ? g4.x : 0.f, gy = fmaf(vy, sc.y, sh.y) > 0.f ? g4.y : 0.f;
+            const float gz = fmaf(vz, sc.z, sh.z) > 0.f ? g4.z : 0.f, gw = fmaf(vw, sc.w, sh.w) > 0.f ? g4.w : 0.f;
+            a.x += gx; a.y += gy; a.z += gz; a.w += gw;
+            b.x += gx * (vx - m.x) * rs.x; b.y += gy * (vy - m.y) * rs.y; b.z += gz * (vz - m.z) * rs.z; b.w += gw * (vw - m.w) * rs.w;
+        }
+    }
+    v4_block_reduce(a, b, sa, sb, part, C, c0, true);
+}
+// dy[r][k][c] = dout[r][c] * scale[c] where k == arg[r][c] and the ReLU was active, else 0
+__global__ __launch_bounds__(256) void bn_maxk_eval_bwd_apply_kernel(const float* __restrict__ dm, int lddm, const int* __restrict__ arg,
+                                                                     const float* __restrict__ y, int ldy, const float* __restrict__ scale,
+                                                                     const float* __restrict__ shift, int C, int K,
+                                                                     float* __restrict__ dy, int lddy, long total /* R * C/4 */) {
+    const int cq = C / 4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / cq;
+        const int c0 = (int)(i - r * cq) * 4;
+        const float4 sc = *reinterpret_cast<const float4*>(scale + c0), sh = *reinterpret_cast<const float4*>(shift + c0);
+        const float4 g4 = *reinterpret_cast<const float4*>(dm + r * lddm + c0);
+        const int4 k4 = *reinterpret_cast<const int4*>(arg + r * C + c0);
+        const float* p = y + r * K * ldy + c0;
+        const float ox = fmaf(p[(long)k4.x * ldy], sc.x, sh.x) > 0.f ? g4.x * sc.x : 0.f, oy = fmaf(p[(long)k4.y * ldy + 1], sc.y, sh.y) > 0.f ? g4.y * sc.y : 0.f;
+        const float oz = fmaf(p[(long)k4.z * ldy + 2], sc.z, sh.z) > 0.f ? g4.z * sc.z : 0.f, ow = fmaf(p[(long)k4.w * ldy + 3], sc.w, sh.w) > 0.f ? g4.w * sc.w : 0.f;
+        float* q = dy + r * K * lddy + c0;
+#pragma unroll 4
+        for (int k = 0; k < K; ++k)
+            *reinterpret_cast<float4*>(q + (long)k * lddy) = make_float4(k == k4.x ? ox : 0.f, k == k4.y ? oy : 0.f, k == k4.z ? oz : 0.f, k == k4.w ? ow : 0.f);
+    }
+}
+// ws: pdf_bn_workspace_floats(C, R) floats when sums are asked for.  dgamma == dbeta == NULL: the apply launch alone.  dy == NULL: sums only.
+// arg must hold indices in [0, K) (what the forward wrote).
+PDF_API int pdf_bn_relu_maxk_eval_bwd(const float* dout, int lddo, const int* arg, const float* y, int ldy,
+                                      const float* running_mean, const float* running_var, float eps, const float* scale, const float* shift,
+                                      int C, long R, int K, float* dy, int lddy, float* dgamma, float* dbeta, int accumulate, float* ws, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (R <= 0 || C <= 0 || K <= 0) return 0;
+    const bool sums = dgamma != nullptr || dbeta != nullptr;
+    if (dout == nullptr || arg == nullptr || y == nullptr || scale == nullptr || shift == nullptr) return PDF_E_BADARG;
+    if (sums && (running_mean == nullptr || running_var == nullptr || ws == nullptr)) return PDF_E_BADARG;
+    if (!v4_ok(C, {ldy, lddo, dy ? lddy : 0}, {y, dout, dy, arg, scale, shift, sums ? running_mean : nullptr, sums ? running_var : nullptr})) return PDF_E_BADARG;
+    if (sums) {
+        long chunks = bn_chunks(C, R);
+        long rpc = (R + chunks - 1) / chunks;
+        chunks = (R + rpc - 1) / rpc;
+        hipLaunchKernelGGL(bn_maxk_eval_bwd_partial_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dout, lddo, arg, y, ldy,
+                           running_mean, running_var, eps, scale, shift, C, K, R, rpc, ws);
+        PDF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, C, dgamma, dbeta, accumulate);
+        PDF_LAUNCH_CHECK();
+    }
+    if (dy != nullptr) {
+        const long total = R * (C / 4);
+        hipLaunchKernelGGL(bn_maxk_eval_bwd_apply_kernel, dim3(grid_for(total)), dim3(256), 0, s, dout, lddo, arg, y, ldy, scale, shift, C, K, dy, lddy, total);
+        PDF_LAUNCH_CHECK();
+    }
     return 0;
 }
 

@@ -994,7 +994,10 @@ class _BatchNorm(Function):
         else:
             L.pdf_bn_eval_fwd(ptr(x), C, C, R, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), eps,
                               ptr(res), C, int(relu), ptr(y), C, ptr(scale), ptr(shift), stream())
-            ctx.save_for_backward(x, gamma, None, None, y if relu else None, None)
+            # frozen statistics: the backward needs (scale, running_mean, running_var) instead of (gamma, mean, rstd).  The running statistics
+            # are saved so that an in-place update of them between forward and backward trips autograd's version check
+            recompute = relu and res is None
+            ctx.save_for_backward(x, scale, rmean, rvar, y if (relu and not recompute) else None, shift if recompute else None)
             ctx.x_is_16 = False
         ctx.cfg = (training, relu, res is not None, eps)
         ctx.params = (gamma, beta)
@@ -1002,14 +1005,14 @@ class _BatchNorm(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, gamma, mean, rstd, y, shift = ctx.saved_tensors
         training, relu, has_res, eps = ctx.cfg
+        if not training:
+            return _BatchNorm._backward_frozen(ctx, dy)
+        x, gamma, mean, rstd, y, shift = ctx.saved_tensors
         scale = None
         mode = int(relu)
         if relu and not has_res:
             scale, y, mode = y, None, 2
-        if not training:
-            raise RuntimeError("pdfnet_amd: BatchNorm backward in eval mode is not implemented")
         R, C = _rows(x)
         g = _canon(dy)
         x_is_16 = ctx.x_is_16
@@ -1035,6 +1038,37 @@ class _BatchNorm(Function):
         if direct:
             dgamma = dbeta = None
         return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None
+
+    @staticmethod
+    def _backward_frozen(ctx, dy):
+        """Eval mode: one pass (pdf_bn_eval_bwd).  Only what ctx.needs_input_grad asks for is computed: frozen affine parameters
+        (requires_grad_(False)) drop the sums and the second launch, an input without gradient drops dx.  No bf16 shadow of dx."""
+        x, scale, rmean, rvar, y, shift = ctx.saved_tensors
+        _, relu, has_res, eps = ctx.cfg
+        mode = (2 if not has_res else 1) if relu else 0
+        need_x, need_g, need_b = ctx.needs_input_grad[:3]
+        need_res = has_res and ctx.needs_input_grad[5]
+        sums = need_g or need_b
+        if not (need_x or sums or need_res):
+            return (None,) * 11
+        R, C = _rows(x)
+        g = _canon(dy)
+        dx = torch.empty_like(x) if need_x else None
+        dres = torch.empty_like(x) if need_res else None
+        dgamma = dbeta = ws = None
+        direct = False
+        if sums:
+            g_par, b_par = ctx.params
+            mg_g, mg_b = _main_grad(g_par, g_par), _main_grad(b_par, b_par)
+            direct = need_g and need_b and mg_g is not None and mg_b is not None
+            dgamma = mg_g if direct else torch.empty(C, device=x.device)
+            dbeta = mg_b if direct else torch.empty(C, device=x.device)
+            ws = _ws(_bn_ws_floats(C, R), x.device)
+        _L().pdf_bn_eval_bwd(ptr(g), C, ptr(y), C, mode, ptr(x), C, ptr(rmean), ptr(rvar), eps, ptr(scale), ptr(shift), C, R,
+                             ptr(dx), C, ptr(dres), C, ptr(dgamma), ptr(dbeta), int(direct), ptr(ws), stream())
+        if direct:
+            dgamma = dbeta = None
+        return dx, (dgamma if need_g else None), (dbeta if need_b else None), None, None, dres, None, None, None, None, None
 
 
 def batch_norm(x, gamma, beta, rmean, rvar, training, momentum=0.1, eps=1e-5, relu=False, res=None, lazy=False):
@@ -1762,17 +1796,18 @@ class _BnReluMaxK(Function):
                    tile_rows=tiles[2] if tiles is not None else None)
         L.pdf_bn_relu_maxk_fwd_x(ptr(x), C, C, R, K, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), momentum, eps, int(training),
                                  ptr(out), C, ptr(arg), ptr(mean), ptr(rstd), ptr(scale), ptr(shift), ptr(ws), stream(), oa)
-        ctx.save_for_backward(x, gamma, arg, mean, rstd, scale, shift)
-        ctx.cfg = (R, K, C, training)
+        # (frozen statistics: the running ones take the place of the batch ones, and autograd's version check guards them)
+        ctx.save_for_backward(x, gamma, arg, mean if training else rmean, rstd if training else rvar, scale, shift)
+        ctx.cfg = (R, K, C, training, eps)
         ctx.params = (gamma, beta)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, gamma, arg, mean, rstd, scale, shift = ctx.saved_tensors
-        R, K, C, training = ctx.cfg
+        R, K, C, training, eps = ctx.cfg
         if not training:
-            raise RuntimeError("pdfnet_amd: BatchNorm backward in eval mode is not implemented")
+            return _BnReluMaxK._backward_frozen(ctx, dout)
+        x, gamma, arg, mean, rstd, scale, shift = ctx.saved_tensors
         g = dout.contiguous()
         dx = torch.empty_like(x)
         g_par, b_par = ctx.params
@@ -1787,6 +1822,32 @@ class _BnReluMaxK(Function):
         if direct:
             dgamma = dbeta = None
         return dx, dgamma, dbeta, None, None, None, None, None, None
+
+    @staticmethod
+    def _backward_frozen(ctx, dout):
+        """Eval mode (pdf_bn_relu_maxk_eval_bwd), computing only what ctx.needs_input_grad asks for -- see _BatchNorm._backward_frozen."""
+        x, _, arg, rmean, rvar, scale, shift = ctx.saved_tensors
+        R, K, C, _, eps = ctx.cfg
+        need_x, need_g, need_b = ctx.needs_input_grad[:3]
+        sums = need_g or need_b
+        if not (need_x or sums):
+            return (None,) * 9
+        g = dout.contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dgamma = dbeta = ws = None
+        direct = False
+        if sums:
+            g_par, b_par = ctx.params
+            mg_g, mg_b = _main_grad(g_par, g_par), _main_grad(b_par, b_par)
+            direct = need_g and need_b and mg_g is not None and mg_b is not None
+            dgamma = mg_g if direct else torch.empty(C, device=x.device)
+            dbeta = mg_b if direct else torch.empty(C, device=x.device)
+            ws = _ws(_bn_ws_floats(C, R), x.device)
+        _L().pdf_bn_relu_maxk_eval_bwd(ptr(g), C, ptr(arg), ptr(x), C, ptr(rmean), ptr(rvar), eps, ptr(scale), ptr(shift), C, R, K,
+                                       ptr(dx), C, ptr(dgamma), ptr(dbeta), int(direct), ptr(ws), stream())
+        if direct:
+            dgamma = dbeta = None
+        return dx, (dgamma if need_g else None), (dbeta if need_b else None), None, None, None, None, None, None
 
 
 def bn_relu_max_over_k(x, gamma, beta, rmean, rvar, K, training, momentum=0.1, eps=1e-5):

@@ -151,11 +151,15 @@ class PointNet_Plus(nn.Module):
         return seq[7].relu_max_over_k(seq[6](x, stats=seq[7].training), K)
 
     @staticmethod
-    def _sa_fused_on(seq):
+    def _sa_fused_on(seq, rows):
         """F.SA_FUSED (PDFNET_SA_FUSED / F.set_sa_fused): levels 1 and 2 run as ONE fused MLP with recomputation (F.sa_mlp_fused) --
-        fp32 mode only: under the bf16 GEMM precision the per-layer path below is kept.  PDFNET_LAZY_SA_BN does not apply to it."""
+        fp32 mode only: under the bf16 GEMM precision the per-layer path below is kept.  PDFNET_LAZY_SA_BN does not apply to it.
+        The fused backward exists for batch statistics only: a level whose BatchNorms are frozen (eval mode) and whose input rows
+        want a gradient takes the per-layer path, which has the frozen-statistics backward."""
         bns = (seq[1], seq[4], seq[7])
-        return F.SA_FUSED and not F._GEMM_BF16 and bns[0].training == bns[1].training == bns[2].training
+        if not (F.SA_FUSED and not F._GEMM_BF16 and bns[0].training == bns[1].training == bns[2].training):
+            return False
+        return bns[0].training or not (torch.is_grad_enabled() and rows.requires_grad)
 
     @staticmethod
     def _sa_fused(seq, rows, S, K, r2):
@@ -204,7 +208,7 @@ class PointNet_Plus(nn.Module):
             e0, emb0 = e0
         pts = self.sft0(cloud, e0)                                                         # [B,1024,3]   (:120-122)
         rows1 = F.pad2d(pts.reshape(-1, 3), pts.shape[0] * pts.shape[1], _pad16(3)).view(pts.shape[0], pts.shape[1], _pad16(3))
-        if self._sa_fused_on(self.netR_1):
+        if self._sa_fused_on(self.netR_1, rows1):
             x = self._sa_fused(self.netR_1, rows1, S1, K, o.ball_radius)                    # [B*S1,128]
         else:
             y1 = self._group_conv(self.netR_1[0], rows1, S1, K, o.ball_radius)             # (:123,:49)
@@ -214,7 +218,7 @@ class PointNet_Plus(nn.Module):
             e1, emb1 = e1
         x = torch.cat((pts[:, :S1], x.view(B, S1, 128), x.new_zeros(B, S1, _pad16(131) - 131)), 2)   # [B,S1,131 | 0]   (:134)
         x = self.sft1(x, e1)                                                               #              (:137)
-        if self._sa_fused_on(self.netR_2):
+        if self._sa_fused_on(self.netR_2, x):
             y = self._sa_fused(self.netR_2, x, S2, K, o.ball_radius2)                        # [B*S2,256]
         else:
             y1 = self._group_conv(self.netR_2[0], x, S2, K, o.ball_radius2)                # (:139,:68)

@@ -102,6 +102,10 @@ class BatchNorm(nn.Module):
         self.register_buffer('running_var', torch.ones(c))
         self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
         self._pending = 0
+        self._frozen = False                                # set by freeze_batchnorm: stays in eval mode through .train()
+
+    def train(self, mode=True):
+        return super().train(bool(mode) and not getattr(self, '_frozen', False))
 
     # `num_batches_tracked += 1` is one launch per layer call (84 per step); the increments are counted on the host and
     # applied by one multi-tensor add (flush_counters: end of HandNET_GCN.forward, and before any state_dict read).
@@ -135,6 +139,18 @@ class BatchNorm(nn.Module):
         """relu(self(x)) followed by the max over groups of K consecutive rows, fused (F.bn_relu_max_over_k)."""
         self.track_call()
         return F.bn_relu_max_over_k(x, self.weight, self.bias, self.running_mean, self.running_var, K, self.training, self.momentum, self.eps)
+
+
+def freeze_batchnorm(module, frozen=True):
+    """Freeze (or thaw) the statistics of every BatchNorm below `module`: a frozen BatchNorm normalises with its running statistics,
+    updates nothing and stays in eval mode through a later `model.train()` -- the usual arrangement for fine-tuning at a small
+    per-GPU batch.  Its weight and bias stay trainable; `requires_grad_(False)` on them is the caller's choice (the backward then
+    skips their sums).  frozen=False thaws: the modules take the mode of `module`.  Returns `module`."""
+    for m in module.modules():
+        if isinstance(m, BatchNorm):
+            m._frozen = bool(frozen)
+            m.train(module.training)
+    return module
 
 
 class LayerNorm(nn.Module):

@@ -139,6 +139,8 @@ class TapedSegment:
             return False
         if not all(m.training for m in self.modules) or F.WGRAD_GROUP > 1 or not (F.ASYNC_WGRAD and F.USE_SIDE_STREAMS):
             return False
+        if not all(b.training for b in self._batchnorms()):    # a frozen BatchNorm inside a train-mode stage (layers.freeze_batchnorm): eager
+            return False
         if not self._params_ok:                                # (checked until it holds once: the Trainer tags its parameters for good)
             for m in self.modules:
                 for p in m.parameters():
@@ -147,11 +149,15 @@ class TapedSegment:
             self._params_ok = True
         return True
 
-    def _count_batchnorms(self):
+    def _batchnorms(self):
         from .networks.layers import BatchNorm
         if self._bns is None:
             self._bns = [b for m in self.modules for b in m.modules() if isinstance(b, BatchNorm)]
-        for b in self._bns:
+        return self._bns
+
+    def _count_batchnorms(self):
+        from .networks.layers import BatchNorm
+        for b in self._batchnorms():
             if b._pending == 0:
                 BatchNorm._dirty.append(b)
             b._pending += 1

@@ -371,6 +371,10 @@ class Trainer:
     def __init__(self, opt, model, loss, lr=1e-4, use_graph=False, broadcast_buffers=False, grad_comm_dtype=None):
         self.opt = opt
         self.model = model
+        if getattr(opt, 'freeze_bn', False):
+            # fine-tuning with frozen BatchNorm statistics: every BatchNorm stays in eval mode through model.train() (layers.freeze_batchnorm)
+            from ..networks.layers import freeze_batchnorm
+            freeze_batchnorm(model)
         self.model_with_loss = ModleWithLoss(model, loss)
         self.model_with_loss.late_join = os.environ.get('PDFNET_MID_LATE_JOIN', '1') != '0'
         # the wh / params heads have no term in CtdetLoss (lib/trains/simplified.py:397-399): under THIS loss they are issued after it and joined
