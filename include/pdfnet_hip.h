@@ -405,6 +405,19 @@ int pdf_dense_loss_bwd(const float* mask, const float* mask_gt, float* dmask, in
  * over the n points (dim 2 or 3) of row r = (sample, hand). */
 int pdf_point_dist_sum(const float* pred, const float* gt, int rows, int n, int dim, float* out, void* stream);
 
+/* ---- aligned evaluation metrics (csrc/metrics.hip) -------------------------------------------- */
+/* Procrustes-aligned point errors, align_w_scale(gt, pred) of lib/utils/eval.py:96-119 per row = (sample, hand): pred, gt [rows][n][3]
+ * metres -> aligned = (pred_c / s2) R^T * s * s1 + t1 with t1, t2 the means, s1, s2 = Frobenius norms of the centred sets + 1e-8,
+ * R = U V^T and s = tr S of (gt_c / s1)^T (pred_c / s2) = U S V^T (scipy's orthogonal_procrustes: no determinant correction, a mirrored
+ * prediction aligns exactly; a rank-deficient product gives finite output).  sum[r] = sum_i dist[r][i], dist[r][i] = ||aligned_i - gt_i||_2;
+ * dist [rows][n] and aligned [rows][n][3] may be NULL.  n <= 1024.  No atomics: two runs are bit-identical. */
+int pdf_procrustes_dist(const float* pred, const float* gt, int rows, int n, float* sum, float* dist, float* aligned, void* stream);
+/* Nearest-neighbour distances behind calculate_fscore (lib/utils/eval.py:54-73): d_gt[r][i] = min_j ||gt_i - pred_j||, d_pred[r][j] =
+ * min_i ||pred_j - gt_i|| ([rows][n], may be NULL) and counts int32 [rows][T][2] = (#{d_gt < thr[t]}, #{d_pred < thr[t]}), strict <.
+ * thr: T thresholds in metres in HOST memory (read during the call), 1 <= T <= 4.  n <= 1024. */
+int pdf_mesh_nn_counts(const float* pred, const float* gt, int rows, int n, const float* thr, int T, int* counts, float* d_gt, float* d_pred,
+                       void* stream);
+
 /* ---- depth front end (csrc/frontend.hip) ------------------------------------------------------ */
 /* depth2pcl (intaghand_encoder.py:369-491 + get_points_coordinate lib/utils/utils.py:251-262) batched on the GPU:
  * depth [B][H][W] metres, mask [B][2][H][W] (right, left), K [B][3][3], valid [B][2] ->

@@ -2393,6 +2393,43 @@ def point_dist_sum(pred, gt):
     return out
 
 
+def _point_sets(name, pred, gt):
+    """pred, gt [..., n, 3] -> detached fp32 contiguous copies and n (the aligned metrics: csrc/metrics.hip keeps a row in LDS, n <= 1024)."""
+    hip.require_gpu(pred, gt)
+    p, q = pred.detach().float().contiguous(), gt.detach().float().contiguous()
+    if p.shape != q.shape or p.dim() < 2 or p.shape[-1] != 3:
+        raise ValueError("pdfnet_amd: %s wants equal shapes [..., n, 3], got %s vs %s" % (name, tuple(p.shape), tuple(q.shape)))
+    if p.shape[-2] > 1024:
+        raise ValueError("pdfnet_amd: %s takes at most 1024 points per set, got %d" % (name, p.shape[-2]))
+    return p, q, p.shape[-2]
+
+
+def procrustes_dist(pred, gt, return_aligned=False):
+    """pred, gt [..., n, 3] -> (sum [...], dist [..., n]) of ||align_w_scale(gt, pred) - gt||_2 (lib/utils/eval.py:96-119: similarity alignment
+    by orthogonal Procrustes, no determinant correction), plus the aligned prediction [..., n, 3] when asked.  No gradient."""
+    p, q, n = _point_sets("procrustes_dist", pred, gt)
+    total = torch.empty(p.shape[:-2], dtype=torch.float32, device=p.device)
+    dist = torch.empty(p.shape[:-1], dtype=torch.float32, device=p.device)
+    aligned = torch.empty_like(p) if return_aligned else None
+    _L().pdf_procrustes_dist(ptr(p), ptr(q), total.numel(), n, ptr(total), ptr(dist), ptr(aligned), stream())
+    return (total, dist, aligned) if return_aligned else (total, dist)
+
+
+def mesh_nn_counts(pred, gt, thresholds, return_dist=False):
+    """pred, gt [..., n, 3], up to four thresholds in metres -> int32 counts [..., T, 2] = (gt points whose nearest predicted point is closer
+    than the threshold, predicted points whose nearest gt point is): the precision / recall numerators of calculate_fscore
+    (lib/utils/eval.py:54-73), strict <.  return_dist: also the two nearest-neighbour distance tensors (d_gt, d_pred) [..., n].  No gradient."""
+    p, q, n = _point_sets("mesh_nn_counts", pred, gt)
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= 4:
+        raise ValueError("pdfnet_amd: mesh_nn_counts takes 1 to 4 thresholds, got %d" % len(thr))
+    counts = torch.empty(p.shape[:-2] + (len(thr), 2), dtype=torch.int32, device=p.device)
+    d_gt, d_pred = (torch.empty(p.shape[:-1], dtype=torch.float32, device=p.device) for _ in range(2)) if return_dist else (None, None)
+    _L().pdf_mesh_nn_counts(ptr(p), ptr(q), counts.numel() // (2 * len(thr)), n, (ctypes.c_float * len(thr))(*thr), len(thr),
+                            ptr(counts), ptr(d_gt), ptr(d_pred), stream())
+    return (counts, d_gt, d_pred) if return_dist else counts
+
+
 # ----------------------------------------------------------------------------------------------
 # Fused mesh decoder (csrc/meshdec.hip, round 5): one DualGraphLayer (DualGraph.py:62-92) = three launches forward, see the kernel file.
 MESH_FUSED = _os.environ.get("PDFNET_MESH_FUSED", "1") != "0"

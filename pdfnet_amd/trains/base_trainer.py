@@ -622,7 +622,7 @@ class Trainer:
         return tot / max(n, 1)
 
 
-    def evaluation(self, loader, device=None, score_path=None, json_path=None):
+    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False):
         """Counterpart of `BaseTrainer.evaluation` (lib/trains/base_trainer.py:207-429, H2O branch): the test-mode pass
         (centres from the predicted heat-map, root from the predicted depth) and the mean Euclidean errors per hand --
         absolute and root-relative joints / vertices in mm, 2-D landmarks in pixels.  The reference evaluates on rank 0
@@ -633,7 +633,11 @@ class Trainer:
         score_path: rank 0 appends the reference's `H2O-val.txt` block (base_trainer.py:420-429).
         json_path:  rank 0 writes the reference's `hand_poses.json` submission file (base_trainer.py:328-335,432-433,486-489):
                     {"modality": "RGBD", "<action id>": {"<frame:06d>.txt": [2 x 21 x 3 absolute joints, left hand first]}};
-                    needs the dataset's `id` / `frame_num` entries in every batch; the predictions of all ranks are gathered."""
+                    needs the dataset's `id` / `frame_num` entries in every batch; the predictions of all ranks are gathered.
+        aligned:    also the figures the hand-mesh literature compares on (the reference carries their arithmetic in lib/utils/eval.py and
+                    eval_util.py but never reaches it, base_trainer.py:396-398): Procrustes-aligned MPJPE / MPVPE, mesh F-scores at
+                    5 / 15 mm and the AUC of the aligned joints' PCK curve -- the keys of `finish_aligned`, from a second device
+                    accumulator that travels with the first (still one all-reduce, one host sync).  The other keys do not change."""
         mwl = self.model_with_loss
         was_training = mwl.training
         mwl.eval()
@@ -642,12 +646,19 @@ class Trainer:
         dev = device or self.optimizer.flat_p.device
         try:
             acc = torch.zeros(11, dtype=torch.float64, device=dev)        # 5 metrics x 2 hands + sample count
+            if aligned:
+                acc2 = torch.zeros(8, dtype=torch.float64, device=dev)    # PA sums and F-score sums, see aligned_sums
+                pck = torch.zeros((21, PCK_STEPS), dtype=torch.int64, device=dev)
             poses = []
             with torch.no_grad():
                 for batch in loader:
                     batch = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
                     tup = mwl(batch, 'test', None)
                     acc += evaluation_sums(tup, batch)
+                    if aligned:
+                        sums, table = aligned_sums(tup)
+                        acc2 += sums
+                        pck += table
                     if json_path is not None:
                         if 'id' not in batch or 'frame_num' not in batch:
                             raise KeyError("Trainer.evaluation: hand_poses.json needs batch['id'] and batch['frame_num'] (interhand.py H2O entries)")
@@ -655,9 +666,14 @@ class Trainer:
                         key = torch.stack((torch.as_tensor(batch['id'], device=dev).reshape(-1).double(),
                                            torch.as_tensor(batch['frame_num'], device=dev).reshape(-1).double()), 1)
                         poses.append(torch.cat((key, jp.reshape(jp.shape[0], -1).double()), 1))          # [B, 2 + 126]
+            if aligned:                                            # one buffer for the reduction and the copy (the counts are exact in float64)
+                acc = torch.cat((acc, acc2, pck.reshape(-1).double()))
             if self.world > 1:
                 dist.all_reduce(acc)
-            out = finish_evaluation(acc.cpu())
+            acc = acc.cpu()
+            out = finish_evaluation(acc[:11])
+            if aligned:
+                out.update(finish_aligned(acc[11:19], acc[19:].reshape(21, PCK_STEPS).round().long(), out['samples']))
             if json_path is not None:
                 rows = torch.cat(poses) if poses else torch.zeros((0, 128), dtype=torch.float64, device=dev)
                 if self.world > 1:                                 # ragged gather: pad every rank's block to the longest
@@ -723,6 +739,75 @@ def write_h2o_scores(path, ev):
             for what in ('joints', 'verts'):
                 for hand in ('left', 'right'):
                     fo.write('%s_%s_%s_loss_all: %.2f\n' % (kind, hand, what, ev['%s_%s_%s' % (kind, hand, what)]))
+
+
+F_THRESHOLDS = (0.005, 0.015)                # mesh F-scores at 5 mm and 15 mm
+PCK_STEPS, PCK_MAX = 100, 0.05               # get_measures(0.0, 0.05, 100) (lib/utils/eval_util.py:53-94): PCK thresholds 0 .. 50 mm
+ALIGNED_KEYS = ('pa_left_joints', 'pa_right_joints', 'pa_left_verts', 'pa_right_verts', 'pa_mpjpe_mm', 'pa_mpvpe_mm',
+                'f5_left', 'f5_right', 'f15_left', 'f15_right', 'f5', 'f15', 'auc_joints')
+_pck_thr = {}
+
+
+def pck_thresholds(device=None):
+    """linspace(0, 0.05, 100) as numpy builds it (float64), or its copy on `device` (made once per device)."""
+    import numpy as np
+    t = np.linspace(0.0, PCK_MAX, PCK_STEPS)
+    if device is None:
+        return t
+    if device not in _pck_thr:
+        _pck_thr[device] = torch.from_numpy(t).to(device)
+    return _pck_thr[device]
+
+
+def fscores(counts, n):
+    """counts [..., 2] of `F.mesh_nn_counts` for sets of n points -> float64 [...]: F = 2pr / (p + r) with precision p = counts[..., 0] / n and
+    recall r = counts[..., 1] / n, 0 where p + r = 0 (calculate_fscore, lib/utils/eval.py:54-73)."""
+    p, r = counts[..., 0].double() / n, counts[..., 1].double() / n
+    return torch.where(p + r > 0, 2 * p * r / (p + r), torch.zeros_like(p))
+
+
+def aligned_sums(tup):
+    """test-mode 9-tuple -> (float64 [8], int64 [21, 100]), all on the device.  The sums over the batch of: the per-sample mean
+    Procrustes-aligned error (`F.procrustes_dist` = align_w_scale, lib/utils/eval.py:96-119) of the absolute joints (left, right) and of the
+    vertices (left, right); the per-sample F-score of the ALIGNED vertices (calculate_fscore, eval.py:54-73: precision = share of gt points
+    with a predicted point closer than the threshold, recall the other way round, F = 2pr / (p + r) or 0) at 5 mm (left, right) and
+    15 mm (left, right).  The table counts per joint the aligned distances of both hands <= each PCK threshold (`_get_pck`: <=)."""
+    vp, jp, vg, jg = tup[:4]
+    js, jd = F.procrustes_dist(jp, jg)                                            # [B,2], [B,2,21]
+    vs, _, va = F.procrustes_dist(vp, vg, return_aligned=True)
+    nv = vp.shape[-2]
+    f = fscores(F.mesh_nn_counts(va, vg, F_THRESHOLDS), nv)                       # [B,2,T]
+    sums = torch.cat(((js.double() / jp.shape[-2]).sum(0), (vs.double() / nv).sum(0), f.sum(0).t().reshape(-1)))
+    table = (jd.double().unsqueeze(-1) <= pck_thresholds(jd.device)).sum((0, 1))
+    return sums, table
+
+
+def finish_aligned(acc, table, n):
+    """The accumulators of `aligned_sums` over n samples -> {'pa_left_joints' ... 'pa_right_verts', 'pa_mpjpe_mm', 'pa_mpvpe_mm' in mm,
+    'f5_left' ... 'f15_right', 'f5', 'f15' (mean per-sample F-score), 'auc_joints' = mean over the keypoints of
+    trapz(pck_j, t) / trapz(1, t) as `get_measures` computes it}; nothing for n = 0."""
+    import numpy as np
+    n = int(n)
+    if n == 0:
+        return {}
+    out = {k: float(acc[i]) / n * (1000 if i < 4 else 1) for i, k in enumerate(ALIGNED_KEYS[:4] + ALIGNED_KEYS[6:10])}
+    out['pa_mpjpe_mm'] = (out['pa_left_joints'] + out['pa_right_joints']) / 2
+    out['pa_mpvpe_mm'] = (out['pa_left_verts'] + out['pa_right_verts']) / 2
+    out['f5'] = (out['f5_left'] + out['f5_right']) / 2
+    out['f15'] = (out['f15_left'] + out['f15_right']) / 2
+    t = pck_thresholds()
+    pck = np.asarray(table, dtype=np.float64) / (2 * n)                          # [21, 100]: both hands of every sample feed a keypoint
+    trapz = lambda y: (np.diff(t) * (y[..., 1:] + y[..., :-1]) / 2.0).sum(-1)
+    out['auc_joints'] = float((trapz(pck) / trapz(np.ones_like(t))).mean())
+    return out
+
+
+def write_aligned_scores(path, ev):
+    """Append the aligned figures of `evaluation(aligned=True)` as a block of their own (`key: %.2f`; the H2O-val.txt block keeps its format)."""
+    with open(path, 'a') as fo:
+        fo.write('eval aligned \n')
+        for k in ALIGNED_KEYS:
+            fo.write('%s: %.2f\n' % (k, ev[k]))
 
 
 def write_hand_poses_json(path, rows):
