@@ -95,6 +95,9 @@ int* pdf_ticket_counters(int n);
 #define PDF_SCRATCH_RING (1L << 26)
 #define PDF_SCRATCH_MAX (1L << 22)
 float* pdf_scratch(long floats);
+// Column sums of a [R][C] matrix through the BatchNorm partial-sum kernels (norm.hip); ws: pdf_internal_colsum_ws(C, R) floats
+int pdf_internal_colsum(const float* g, int ldg, int C, long R, float* out, int accumulate, float* ws, hipStream_t s);
+long pdf_internal_colsum_ws(int C, long R);
 // bf16 packing: the shadows (PdfCallOpts below) and the x3 components are written with these
 typedef __bf16 pdf_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float pdf_f32x2 __attribute__((ext_vector_type(2)));

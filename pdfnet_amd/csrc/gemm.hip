@@ -12,17 +12,8 @@
 #include "common.h"
 
 #include "gemm_common.h"
+#include "gemm_internal.h"
 
-// winograd.hip
-long pdf_internal_wino_workspace(int N, int H, int W, int Ck, int Cn, int flip);
-int pdf_internal_wino_eligible(int N, int H, int W, int Ck, int Cn, int KH, int KW, int stride, int pad, int flip);
-int pdf_internal_conv3x3_winograd(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, float* ws,
-                                  int N, int H, int W, int Ck, int Cn, int act, int accum, int flip, const float* v_shared, hipStream_t s);
-int pdf_internal_wino_wgrad_eligible(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
-long pdf_internal_wino_wgrad_workspace(int N, int H, int W, int Cin, int Cout);
-long pdf_internal_wino_v_offset(int N, int H, int W, int Ck, int Cn);
-int pdf_internal_conv3x3_winograd_wgrad(const float* x, int ldx, const float* dy, int lddy, float* dw, float* db, float* ws,
-                                        int N, int H, int W, int Cin, int Cout, int accumulate, const float* v_cached, hipStream_t s);
 // Workspace (floats) a stride-1 3x3 convolution [Cout][3][3][Cin] on N x H x W maps wants for its Winograd path -- backward = 0: the
 // forward pass, 1: backward-data, 2: the weight gradient -- or 0 when the layer does not qualify (then no workspace is needed)
 PDF_API long pdf_conv2d_winograd_v_offset(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
@@ -35,28 +26,8 @@ PDF_API long pdf_conv2d_winograd_workspace_floats(int N, int H, int W, int Cin, 
     return pdf_internal_wino_eligible(N, H, W, Ck, Cn, KH, KW, stride, pad, backward) ? pdf_internal_wino_workspace(N, H, W, Ck, Cn, backward) : 0;
 }
 
-// Read the LDS fragments of the next k-pair while the MFMAs of the current one run (see igemm_nt).  Compile-time switch for A/B runs.
-#ifndef PDF_FRAG_PIPE
-#define PDF_FRAG_PIPE 0
-#endif
-constexpr bool FRAG_PIPE = PDF_FRAG_PIPE != 0;
-#ifndef PDF_WG_ISSUE_AT
-#define PDF_WG_ISSUE_AT 1                       // wgemm_tn_dma, scalar-offset form: the k-pair after which the next tile's loads are issued
-#endif
-#ifndef PDF_IG_DEEP
-#define PDF_IG_DEEP 1
-#endif
-constexpr bool IG_DEEP = PDF_IG_DEEP != 0;      // igemm_nt, buffer-load form: two K-steps of prefetch in flight
-// Round 5: operand fragments as ONE ds_read_b128 per 32 rows and 8 k.  Lane l reads the four consecutive k of chunk (l >> 5) of row (l & 31);
-// MFMA t of the group pairs k = 8 g + t (lanes 0-31) with k = 8 g + 4 + t (lanes 32-63) -- any pairing is a valid reduction order as long
-// as A and B use the same.  Rows are BK + 4 floats apart (16-byte aligned, stride = 4 mod 8 floats: conflict-free for b128), so the staging
-// store is one ds_write_b128 per thread and row too: 4x fewer LDS instructions on both sides than the [BK + 1] image with scalar accesses.
-// MEASURED (profiles/r05_ig_b128.txt): no layer gains, the [K][N] backward-data forms lose 5-10 %, the step 50.7 vs 49.8 ms -- LDS instruction
-// issue is not what bounds these loops (the what-if builds of round 3 said the same of the loads).  Off; kept as a compile-time switch.
-#ifndef PDF_IG_B128
-#define PDF_IG_B128 0
-#endif
-constexpr bool IG_B128 = PDF_IG_B128 != 0;
+constexpr int WG_ISSUE_AT = 1;                  // wgemm_tn_dma, scalar-offset form: the k-pair after which the next tile's loads are issued
+// (Measured and rejected: ds_read_b128 fragments over a [BK + 4] image and fragment reads pipelined one k-pair ahead -- profiles/r05_ig_b128.txt.)
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 as_f4(const u32x4v& v) { return *reinterpret_cast<const float4*>(&v); }
 
@@ -70,7 +41,7 @@ __device__ __forceinline__ float4 as_f4(const u32x4v& v) { return *reinterpret_c
 template <int BM, int BN, int WM, int WN, bool FAST, bool KN, int BKT, bool BUF, bool AFF>
 __device__ __forceinline__ void igemm_nt_body(const IGemm& g) {    // (128x128: 3 waves per SIMD = 3 blocks per CU, as its LDS allows)
     constexpr int NT = WM * WN * 64;                     // threads: one wave per (BM/WM) x (BN/WN) sub-tile
-    constexpr int BK = BKT, LD = IG_B128 ? BK + 4 : BK + 1;      // K-step: 16, or 32 for the small tile (half the barriers per flop)
+    constexpr int BK = BKT, LD = BK + 1;      // K-step: 16, or 32 for the small tile (half the barriers per flop)
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int TPR = BK / 4, RPP = NT / TPR;          // threads per staged row (a float4 each), rows per pass of the block
     constexpr int RA = BM / RPP, RB = BN / RPP;
@@ -135,7 +106,7 @@ __device__ __forceinline__ void igemm_nt_body(const IGemm& g) {    // (128x128: 
     if (g.ksteps > 0) { kt0 = blockIdx.z * g.ksteps; kt1 = min(nk, kt0 + g.ksteps); }
 
     float4 ra[RA], rb[RB];
-    float4 ra1[RA], rb1[RB];                             // second register set of the two-steps-ahead prefetch (IG_DEEP)
+    float4 ra1[RA], rb1[RB];                             // second register set of the two-steps-ahead prefetch
     int nload = kt0;                                     // K-step the next gload fetches (BUF: a step past kt1 loads zeros, no traffic)
     // tap state of the NEXT tile to load (tiles are loaded strictly in order): no per-tile division and the
     // tap table (scalar loads that share lgkmcnt with the LDS traffic) is read only when the tap changes
@@ -250,8 +221,7 @@ __device__ __forceinline__ void igemm_nt_body(const IGemm& g) {    // (128x128: 
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             float* p = &As[buf][(lrow + i * RPP) * LD + kq];
-            if constexpr (IG_B128) *reinterpret_cast<float4*>(p) = ra[i];
-            else { p[0] = ra[i].x; p[1] = ra[i].y; p[2] = ra[i].z; p[3] = ra[i].w; }
+            p[0] = ra[i].x; p[1] = ra[i].y; p[2] = ra[i].z; p[3] = ra[i].w;
         }
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
@@ -260,60 +230,31 @@ __device__ __forceinline__ void igemm_nt_body(const IGemm& g) {    // (128x128: 
                 p[0] = rb[i].x; p[LD] = rb[i].y; p[2 * LD] = rb[i].z; p[3 * LD] = rb[i].w;
             } else {
                 float* p = &Bs[buf][(lrow + i * RPP) * LD + kq];
-                if constexpr (IG_B128) *reinterpret_cast<float4*>(p) = rb[i];
-                else { p[0] = rb[i].x; p[1] = rb[i].y; p[2] = rb[i].z; p[3] = rb[i].w; }
+                p[0] = rb[i].x; p[1] = rb[i].y; p[2] = rb[i].z; p[3] = rb[i].w;
             }
         }
     };
 
-    const int arow = (wm * TM * 32 + (lane & 31)) * LD + (lane >> 5) * (IG_B128 ? 4 : 1);
-    const int brow = (wn * TN * 32 + (lane & 31)) * LD + (lane >> 5) * (IG_B128 ? 4 : 1);
+    const int arow = (wm * TM * 32 + (lane & 31)) * LD + (lane >> 5);
+    const int brow = (wn * TN * 32 + (lane & 31)) * LD + (lane >> 5);
     auto compute = [&](int cur) {
         const float* as = As[cur];
         const float* bs = Bs[cur];
-        if constexpr (IG_B128) {
-#pragma unroll
-            for (int g8 = 0; g8 < BK / 8; ++g8) {
-                float4 a4[TM], b4[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) a4[i] = *reinterpret_cast<const float4*>(as + arow + i * 32 * LD + g8 * 8);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b4[j] = *reinterpret_cast<const float4*>(bs + brow + j * 32 * LD + g8 * 8);
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            const float av = t == 0 ? a4[i].x : t == 1 ? a4[i].y : t == 2 ? a4[i].z : a4[i].w;
-                            const float bv = t == 0 ? b4[j].x : t == 1 ? b4[j].y : t == 2 ? b4[j].z : b4[j].w;
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                        }
-            }
-            return;
-        }
-        // fragments of k-pair kk + 1 are read while the MFMAs of pair kk run (two register sets, FRAG_PIPE)
-        float a[2][TM], b[2][TN];
-        auto frag = [&](int set, int kk) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[set][i] = as[arow + i * 32 * LD + kk * 2];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[set][j] = bs[brow + j * 32 * LD + kk * 2];
-        };
-        if (FRAG_PIPE) frag(0, 0);
 #pragma unroll
         for (int kk = 0; kk < BK / 2; ++kk) {
-            const int set = FRAG_PIPE ? (kk & 1) : 0;
-            if (FRAG_PIPE) { if (kk + 1 < BK / 2) frag(set ^ 1, kk + 1); }
-            else frag(0, kk);
+            float a[TM], b[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) a[i] = as[arow + i * 32 * LD + kk * 2];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) b[j] = bs[brow + j * 32 * LD + kk * 2];
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[set][i], b[set][j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
         }
     };
-    if constexpr (FAST && BUF && IG_DEEP && BM * BN <= 64 * 64) {      // (wider tiles: the compiler doubles the accumulator registers across the two phases)
+    if constexpr (FAST && BUF && BM * BN <= 64 * 64) {      // (wider tiles: the compiler doubles the accumulator registers across the two phases)
         // two K-steps in flight: while step kt is computed from LDS, step kt + 1 sits in one register set and the loads of step
         // kt + 2 have just been issued into the other -- short reductions (1x1 layers, K = 64 ... 256) expose one memory latency
         // per tile instead of one per step.  All loads are issued unconditionally (a step past the end reads zeros through the
@@ -563,23 +504,22 @@ __global__ __launch_bounds__(256, 3) void igemm_halo3x3(const IGemm g) {
         const int toff = (g.dy[tap] * HC + g.dx[tap]) * LD;
         const float* as = As[abuf] + toff;
         const float* bs = Bs[bbuf];
+        // ([2]: only row 0 is used.  With a[TM] / b[TN] the flat-address forms of this kernel zero their accumulators in another order, and
+        // this change keeps every implicit-GEMM kernel's code as it was; igemm_nt_body shows no such dependence.)
         float a[2][TM], b[2][TN];
-        auto frag = [&](int set, int kk) {
+        auto frag = [&](int kk) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i) a[set][i] = as[arow[i] + kk * 2];
+            for (int i = 0; i < TM; ++i) a[0][i] = as[arow[i] + kk * 2];
 #pragma unroll
-            for (int j = 0; j < TN; ++j) b[set][j] = bs[brow + j * 32 * LD + kk * 2];
+            for (int j = 0; j < TN; ++j) b[0][j] = bs[brow + j * 32 * LD + kk * 2];
         };
-        if (FRAG_PIPE) frag(0, 0);
 #pragma unroll
         for (int kk = 0; kk < BK / 2; ++kk) {
-            const int set = FRAG_PIPE ? (kk & 1) : 0;
-            if (FRAG_PIPE) { if (kk + 1 < BK / 2) frag(set ^ 1, kk + 1); }
-            else frag(0, kk);
+            frag(kk);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[set][i], b[set][j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0][i], b[0][j], acc[i][j], 0, 0, 0);
         }
         if (more) bstore(bbuf ^ 1);
         if (stage_a) hstore(abuf ^ 1);
@@ -838,8 +778,7 @@ __device__ __forceinline__ void wgemm_tn_body(const WGemm& g) {
         cur ^= 1;
     }
 
-    // (the ticket flag lives in the staging array: a second __shared__ object can de-pipeline LDS-DMA kernels, guide section 5 item 4a)
-    wgemm_finish<TM, TN>(g, acc, i0, j0, wm, wn, lane, do_bias && i0 + tid < g.NI, bsum, ti * ntj + tj, nti * ntj, reinterpret_cast<int*>(&Ps[0][0]), i0 + BI <= g.NI);
+    wgemm_finish<TM, TN>(g, acc, i0, j0, wm, wn, lane, do_bias && i0 + tid < g.NI, bsum, i0 + BI <= g.NI);
 }
 
 
@@ -1097,7 +1036,8 @@ __device__ __forceinline__ void wgemm_tn_dma_body(const WGemm& g) {
     int st = 0, stn = ST - 1;
     for (int t = 0; t < nt; ++t) {
         // this wave's 4 DMAs of tile t have landed (the ST-2 younger tiles may still fly) ...
-        if (ST == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        static_assert(ST == 3, "the counted wait below is for two tiles of 4 DMAs in flight");
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         __builtin_amdgcn_s_barrier();                       // ... and everybody's; everybody also finished reading tile t-1
         // refill the stage tile t-1 used (rows past the end read zeros).  The scalar-offset form is issued from INSIDE the MFMA
         // sequence (after the second k-pair): its ~25 scalar / vector instructions and 4 DMA loads then overlap the matrix pipe
@@ -1109,37 +1049,30 @@ __device__ __forceinline__ void wgemm_tn_dma_body(const WGemm& g) {
 #pragma unroll
             for (int kb = 0; kb < BK; ++kb) bsum += ps[kb * 128 + tid];
         }
-        float a[2][TM], b[2][TN];
-        auto frag = [&](int set, int kk) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[set][i] = ps[aoff + kk * 2 * 128 + i * 32];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[set][j] = qs[boff + kk * 2 * 128 + j * 32];
-            if constexpr (qaff) {                            // WGemm::q_scale: BatchNorm + ReLU of x at fragment-read time (every K-step is whole here)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b[set][j] = fmaxf(fmaf(b[set][j], fsc[j], fsh[j]), 0.f);
-            }
-        };
-        if (FRAG_PIPE) frag(0, 0);
 #pragma unroll
         for (int kk = 0; kk < BK / 2; ++kk) {
-            const int set = FRAG_PIPE ? (kk & 1) : 0;
-            if (FRAG_PIPE) { if (kk + 1 < BK / 2) frag(set ^ 1, kk + 1); }
-            else frag(0, kk);
+            float a[TM], b[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) a[i] = ps[aoff + kk * 2 * 128 + i * 32];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) b[j] = qs[boff + kk * 2 * 128 + j * 32];
+            if constexpr (qaff) {                            // WGemm::q_scale: BatchNorm + ReLU of x at fragment-read time (every K-step is whole here)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) b[j] = fmaxf(fmaf(b[j], fsc[j], fsh[j]), 0.f);
+            }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[set][i], b[set][j], acc[i][j], 0, 0, 0);
-            if (kk == PDF_WG_ISSUE_AT && u16) issue_u16(t + ST - 1, stn);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+            if (kk == WG_ISSUE_AT && u16) issue_u16(t + ST - 1, stn);
         }
         st = st == ST - 1 ? 0 : st + 1;
         stn = stn == ST - 1 ? 0 : stn + 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA may outlive the workgroup
 
-    wgemm_finish<TM, TN>(g, acc, i0, j0, wm, wn, lane, do_bias && i0 + tid < g.NI, bsum, ti * ntj + tj, nti * ntj, reinterpret_cast<int*>(smem), i0 + 128 <= g.NI,
-                         lin_tile >= 0 ? split : -1, plane);
+    wgemm_finish<TM, TN>(g, acc, i0, j0, wm, wn, lane, do_bias && i0 + tid < g.NI, bsum, i0 + 128 <= g.NI, lin_tile >= 0 ? split : -1, plane);
 }
 
 template <int ST, bool BUF>
@@ -1198,10 +1131,11 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // Tuning overrides for tools/gemm_bench.py sweeps.  The environment is read ONCE (std::call_once: the main thread and the
 // autograd thread both launch GEMMs); an unset variable stays "unset", so every call site applies its OWN default --
 // several sites pass shape-dependent defaults (round-1 bug: the first caller's default was cached for everybody).
-enum { ENV_IG_T128, ENV_IG_BK32, ENV_WG_TARGET, ENV_WG_MINROWS, ENV_WG_TAPMAJOR, ENV_WG_BK32, ENV_WG_DMA, ENV_IG_HALO_MINC, ENV_IG_HALO, ENV_IG_T32, ENV_WG_INLAUNCH, ENV_WG_QUANT, ENV_IG_SPLITK, ENV_WG_LDSPAD, ENV_IG_SHORTK, ENV_WG_ATOMIC, ENV_WG_STEM, ENV_IG_SPLITK_MAXT, ENV_IG_SPLITK_TARGET, ENV_WG_SLOTS, ENV_WG_BUF, ENV_IG_BUF, ENV_WG_UNIFORM, ENV_IG_BUFSTORE, ENV_IG_BF16_STATS, ENV_IG_DMA, ENV_IG_DMA128, ENV_WG_BATCH_XCD, ENV_IG_GROUPM, ENV_COUNT };
+enum { ENV_IG_T128, ENV_IG_BK32, ENV_WG_MINROWS, ENV_WG_TAPMAJOR, ENV_WG_BK32, ENV_IG_HALO_MINC, ENV_IG_HALO, ENV_IG_T32, ENV_IG_SPLITK, ENV_IG_SHORTK, ENV_WG_STEM, ENV_IG_SPLITK_MAXT, ENV_IG_SPLITK_TARGET, ENV_WG_BUF, ENV_IG_BUF, ENV_WG_UNIFORM, ENV_IG_BUFSTORE, ENV_IG_BF16_STATS, ENV_WG_BATCH_XCD, ENV_IG_GROUPM, ENV_COUNT };
 static int env_int(int which, int dflt) {
-    static const char* const names[ENV_COUNT] = {"PDF_IG_T128", "PDF_IG_BK32", "PDF_WG_TARGET", "PDF_WG_MINROWS", "PDF_WG_TAPMAJOR",
-                                                 "PDF_WG_BK32", "PDF_WG_DMA", "PDF_IG_HALO_MINC", "PDF_IG_HALO", "PDF_IG_T32", "PDF_WG_INLAUNCH", "PDF_WG_QUANT", "PDF_IG_SPLITK", "PDF_WG_LDSPAD", "PDF_IG_SHORTK", "PDF_WG_ATOMIC", "PDF_WG_STEM", "PDF_IG_SPLITK_MAXT", "PDF_IG_SPLITK_TARGET", "PDF_WG_SLOTS", "PDF_WG_BUF", "PDF_IG_BUF", "PDF_WG_UNIFORM", "PDF_IG_BUFSTORE", "PDF_IG_BF16_STATS", "PDF_IG_DMA", "PDF_IG_DMA128", "PDF_WG_BATCH_XCD", "PDF_IG_GROUPM"};
+    static const char* const names[ENV_COUNT] = {"PDF_IG_T128", "PDF_IG_BK32", "PDF_WG_MINROWS", "PDF_WG_TAPMAJOR", "PDF_WG_BK32", "PDF_IG_HALO_MINC", "PDF_IG_HALO", "PDF_IG_T32",
+                                                 "PDF_IG_SPLITK", "PDF_IG_SHORTK", "PDF_WG_STEM", "PDF_IG_SPLITK_MAXT", "PDF_IG_SPLITK_TARGET", "PDF_WG_BUF", "PDF_IG_BUF", "PDF_WG_UNIFORM",
+                                                 "PDF_IG_BUFSTORE", "PDF_IG_BF16_STATS", "PDF_WG_BATCH_XCD", "PDF_IG_GROUPM"};
     static int vals[ENV_COUNT];
     static std::once_flag once;
     std::call_once(once, [] {
@@ -1444,9 +1378,7 @@ static int launch_igemm(IGemm& g, hipStream_t s, int groups = 1, PdfCallOpts* co
                 IGemm gs = g;
                 gs.ksteps = ksteps; gs.part = part;
                 const dim3 grid((unsigned)t64, 1, (unsigned)splits);
-                const int dma = env_int(ENV_IG_DMA, 0);
-                if (dma > 0 && fast && bk32 && launch_igemm_dma(gs, 64, dma - 1, 1, splits, s)) {}
-                else if (bk32) launch_igemm_tile<64, 64, 2, 2, 32>(gs, fast, grid, s);
+                if (bk32) launch_igemm_tile<64, 64, 2, 2, 32>(gs, fast, grid, s);
                 else launch_igemm_tile<64, 64, 2, 2>(gs, fast, grid, s);
                 KTimer kt("splitk_finish", 0.0, 4.0 * (splits + 1) * g.M * g.N, s);
                 hipLaunchKernelGGL(splitk_finish, dim3(grid_for((long)g.M * g.N)), dim3(256), 0, s, part, splits, g.M, g.N, g.bias, g.act, g.C, g.ldc);
@@ -1487,9 +1419,7 @@ static int launch_igemm(IGemm& g, hipStream_t s, int groups = 1, PdfCallOpts* co
     }
     else if (g.N > 64 && t128 >= env_int(ENV_IG_T128, 600) && !short_k) {
         stat_plan(g, co, 128);
-        const int dma = env_int(ENV_IG_DMA128, 0);
-        if (!(dma > 0 && fast && g.batch == 0 && launch_igemm_dma(g, 128, dma - 1, groups, 0, s)))
-            launch_igemm_tile<128, 128, 2, 2>(g, fast, dim3(cdiv(g.M, 128) * cdiv(g.N, 128), groups), s);
+        launch_igemm_tile<128, 128, 2, 2>(g, fast, dim3(cdiv(g.M, 128) * cdiv(g.N, 128), groups), s);
         g_last_tile = 128128;
     }
     else if (g.N <= 64 && (long)cdiv(g.M, 128) * groups >= env_int(ENV_IG_T128, 600))
@@ -1504,13 +1434,11 @@ static int launch_igemm(IGemm& g, hipStream_t s, int groups = 1, PdfCallOpts* co
     {
         stat_plan(g, co, 64);
         const dim3 grid(cdiv(g.M, 64) * cdiv(g.N, 64), groups);
-        const int dma = env_int(ENV_IG_DMA, 0);
         // K-step 32 for the small tile: its 8 MFMAs per wave and 16-wide step leave the barrier exposed (l4 3x3: 62 -> 72 TFLOP/s)
         // (a deep-ring form for the mesh decoder's latency-bound products -- the whole reduction in flight before the first MFMA, 4-8 stages
         // of the LDS-DMA kernel on <= 512 / 1024 tiles -- was measured: the pair entry points unchanged, the step 0.5-3 % slower;
         // profiles/r04_igemm_dma_ab.txt)
-        if (dma > 0 && fast && g.batch == 0 && launch_igemm_dma(g, 64, dma - 1, groups, 0, s)) {}      // (batch == 0: igemm_dma reads blockIdx.y as the pair index, not as a plane of a batched launch -- it faulted on the Winograd products, round 6)
-        else if (fast && g.Cin % 32 == 0 && env_int(ENV_IG_BK32, 1)) launch_igemm_tile<64, 64, 2, 2, 32>(g, fast, grid, s);
+        if (fast && g.Cin % 32 == 0 && env_int(ENV_IG_BK32, 1)) launch_igemm_tile<64, 64, 2, 2, 32>(g, fast, grid, s);
         else launch_igemm_tile<64, 64, 2, 2>(g, fast, grid, s);
         g_last_tile = 64064;
     }
@@ -1557,19 +1485,6 @@ int pdf_internal_batched_gemm(const float* A, const float* B, float* C, int batc
     return launch_igemm(g, s, batch);
 }
 
-long pdf_internal_x3_deconv_workspace(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int backward);
-int pdf_internal_x3_deconv_fwd(const float* x, const float* w, const float* bias, float* y, float* ws, int N, int H, int W, int Cin, int Cout,
-                               int KH, int KW, int stride, int OH, int OW, int ldy, hipStream_t s);
-int pdf_internal_x3_deconv_bwd_data(const float* dy, const float* w, float* dx, float* ws, int N, int H, int W, int Cin, int lddx, int Cout,
-                                    int KH, int KW, int stride, int OH, int OW, int lddy, hipStream_t s);
-int pdf_internal_x3_deconv_general_fwd(const float* x, const float* w, const float* bias, float* y, float* ws, int N, int H, int W, int Cin, int Cout,
-                                       int K, int stride, int pad, int OH, int OW, int ldy, hipStream_t s);
-int pdf_internal_x3_deconv_general_bwd_data(const float* dy, const float* w, float* dx, float* ws, int N, int H, int W, int Cin, int lddx, int Cout,
-                                            int K, int stride, int pad, int OH, int OW, int lddy, hipStream_t s);
-int pdf_internal_x3_deconv_general_bwd_weight(const float* x, const float* dy, float* dw, float* ws, int N, int H, int W, int Cin, int Cout,
-                                              int K, int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s);
-int pdf_internal_x3_deconv_bwd_weight(const float* x, const float* dy, float* dw, float* ws, int N, int H, int W, int Cin, int Cout,
-                                      int KH, int KW, int stride, int OH, int OW, int lddy, int accumulate, hipStream_t s);
 PDF_API long pdf_deconv2d_x3_workspace_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int backward) {
     return g_gemm_bf16 ? 0 : pdf_internal_x3_deconv_workspace(N, H, W, Cin, Cout, KH, KW, stride, pad, backward);
 }
@@ -2065,42 +1980,21 @@ static int launch_wgemm(WGemm& g, float* out, float* ws, long ws_floats, int acc
     // efficiency.  wg_choose_splits() prices every candidate with a small model (blocks on the busiest CU, efficiency of 1 / 2 /
     // 3 / 4 co-resident blocks, a fixed cost per block, the slab reduction) and stays within one round.  Measured with it
     // (tools/gemm_bench.py, TFLOP/s): feat 104.8 -> 112, p2 / hm 102.6 -> 116, decoder 3x3 88.9 -> 101, l3 3x3 70.8 -> 82.6,
-    // l4 3x3 71.7 -> 82.3; PDF_WG_TARGET=<blocks> restores the r02 rule.
-    const bool bf16_mode = g_gemm_bf16 && fast;
-    const int occ = env_int(ENV_WG_SLOTS, 0) > 0 ? max(1, min(4, env_int(ENV_WG_SLOTS, 0) / 256)) : (bf16_mode ? (small ? 3 : 2) : (small ? 4 : 3));      // (the efficiency table of wg_choose_splits covers 1-4 co-resident blocks)
-    const int target = env_int(ENV_WG_TARGET, 0);
-    int splits = target > 0 ? (int)((target + tiles * groups - 1) / (tiles * groups)) : 0;
-    int max_by_rows = cdiv(g.M, env_int(ENV_WG_MINROWS, g.M >= 16384 ? 512 : 128));
-    if (splits > max_by_rows) splits = max_by_rows;
+    // l4 3x3 71.7 -> 82.3.
+    const bool bf16 = g_gemm_bf16 && fast;
+    const int occ = bf16 ? (small ? 3 : 2) : (small ? 4 : 3);      // (the efficiency table of wg_choose_splits covers 1-4 co-resident blocks)
+    const int rq = bf16 ? 64 : 16;                          // row quantum of a split
     long per = (long)g.NI * g.ldw;
     const long perb = db ? g.NI : 0;
-    if (target > 0 && (long)splits * (per + perb) * groups > ws_floats) splits = (int)(ws_floats / ((per + perb) * groups));
-    const bool bf16 = g_gemm_bf16 && fast;
-    if (target <= 0) {
-        int cap = max_by_rows;
-        if ((long)cap * (per + perb) * groups > ws_floats) cap = (int)(ws_floats / ((per + perb) * groups));
-        splits = wg_choose_splits(tiles * groups, g.M, occ, max(cap, 1), bf16 ? 64 : 16, small ? 64 : 128, (double)(per + perb) * 4.0);
-    }
+    int cap = cdiv(g.M, env_int(ENV_WG_MINROWS, g.M >= 16384 ? 512 : 128));
+    if ((long)cap * (per + perb) * groups > ws_floats) cap = (int)(ws_floats / ((per + perb) * groups));
+    int splits = wg_choose_splits(tiles * groups, g.M, occ, max(cap, 1), rq, small ? 64 : 128, (double)(per + perb) * 4.0);
     if (splits < 1) splits = 1;
     if (!bf16 || groups > 1) { g.P16 = nullptr; g.Q16 = nullptr; }
     if (db != nullptr) g.P16 = nullptr;                     // the fused bias gradient sums the un-rounded rows of P
     // (16-byte groups of 8 bf16 along the operand's columns)
     if (g.P16 != nullptr && ((reinterpret_cast<uintptr_t>(g.P16) & 15) || g.ldp % 8 || g.NI % 8 || g.gsP % 8)) g.P16 = nullptr;
     if (g.Q16 != nullptr && ((reinterpret_cast<uintptr_t>(g.Q16) & 15) || g.ldq % 8 || g.Cq % 8 || g.gsQ % 8)) g.Q16 = nullptr;
-    const int rq = bf16 ? 64 : 16;
-    // The blocks all run equally long and the chip retires them CU by CU: 1044 blocks on 256 CUs leave most CUs idle for the
-    // fifth pass (82 % busy).  Among split counts down to 3/4 of the target, take the one whose block count fills whole
-    // passes best (never more splits than the workspace was sized for).
-    if (splits > 1 && target > 0 && env_int(ENV_WG_QUANT, 1)) {
-        int best = splits; double beste = -1.0;
-        for (int sp = splits; sp >= 1 && sp * 4 >= splits * 3; --sp) {
-            const int r = cdiv(cdiv(g.M, sp), rq) * rq;
-            const long blocks = tiles * groups * cdiv(g.M, r);
-            const double e = (double)blocks / (256.0 * (double)((blocks + 255) / 256));
-            if (e > beste + 0.02) { beste = e; best = sp; }
-        }
-        splits = best;
-    }
     int rps = cdiv(cdiv(g.M, splits), rq) * rq;
     splits = cdiv(g.M, rps);
     g.rows_per_split = rps;
@@ -2112,18 +2006,6 @@ static int launch_wgemm(WGemm& g, float* out, float* ws, long ws_floats, int acc
     g.bslab1 = db ? (splits == 1 ? db1 : bws + (long)splits * perb) : nullptr;
     g.beta = splits == 1 ? accumulate : 0;
     g.wbytes = (4.0 * g.NI * g.ldw < 4294967000.0 && env_int(ENV_IG_BUFSTORE, 1)) ? (unsigned)(4.0 * g.NI * g.ldw) : 0;
-    g.out = out; g.out1 = out1; g.bout = db; g.bout1 = db1; g.accumulate = accumulate;
-    // In-launch reduction (PDF_WG_INLAUNCH=1) is OFF by default: measured 245 vs 395 img/s.  Every block's agent-scope release
-    // fence (buffer_wbl2) writes back the whole XCD L2, which holds megabytes of slabs and of the main stream's fresh outputs;
-    // write-through slab stores would need 16-byte stores from a re-laid-out accumulator (4-byte sc1 stores are ~6x slower).
-    // BatchNorm's in-launch finalisation (norm.hip) publishes 32 bytes per block and does use the write-through form.
-    g.counters = (splits > 1 && env_int(ENV_WG_INLAUNCH, 0)) ? pdf_ticket_counters((int)tiles * groups) : nullptr;
-    // Optional (PDF_WG_ATOMIC = minimum split count; default: never): accumulating launches add their partial tiles with fp32
-    // atomics instead of writing slabs -- no slab round trip, no reduce_slabs launch (-133 launches, -2.1 ms of side-stream work
-    // per step).  Measured: fp32 B=32 420.4 / 421.3 without vs 417.9 / 420.5 with, RGB-only encoder B=8 483 vs 473, bf16 B=64
-    // 862 vs 865 -- the reductions run on the side stream beside MFMA-bound kernels and cost nothing there, the atomic
-    // read-modify-writes cost the weight-gradient kernels' epilogues more than plain stores.
-    g.atomic = (splits >= env_int(ENV_WG_ATOMIC, 1 << 30) && splits > 1 && accumulate && g.counters == nullptr) ? 1 : 0;
     dim3 grid((unsigned)tiles, (unsigned)splits, (unsigned)groups);
     int brc = 0;
     const double wflops = 2.0 * groups * g.M * g.NI * NJ, wbytes = wgemm_bytes(g, groups);
@@ -2152,24 +2034,20 @@ static int launch_wgemm(WGemm& g, float* out, float* ws, long ws_floats, int acc
         else if (fast) hipLaunchKernelGGL((wgemm_tn<64, 64, 2, 2, true>), grid, dim3(256), 0, s, g);
         else hipLaunchKernelGGL((wgemm_tn<64, 64, 2, 2, false>), grid, dim3(256), 0, s, g);
     } else {
-        const int dma = env_int(ENV_WG_DMA, 3);
-        const int pad = env_int(ENV_WG_LDSPAD, 0) * 1024;
-        const bool buf = fast && dma == 3 && pext < 4294967000.0 && qext < 4294967000.0 && env_int(ENV_WG_BUF, 1);
+        const bool buf = fast && pext < 4294967000.0 && qext < 4294967000.0 && env_int(ENV_WG_BUF, 1);
         g.pbytes = buf ? (unsigned)pext : 0; g.qbytes = buf ? (unsigned)qext : 0;
         g.uniform = (buf && (g.plain_q || (g.QW % 8 == 0 && g.Cq % 128 == 0)) && env_int(ENV_WG_UNIFORM, 2)) ? 1 : 0;
         if (g.uniform && env_int(ENV_WG_UNIFORM, 2) >= 2 && g.rows_per_split % 16 == 0 && g.M % 16 == 0 && (g.plain_q || g.QW % 16 == 0)) g.uniform = 2;
         if (g.q_scale != nullptr && g.uniform != 2) return PDF_E_BADARG;      // (the fragment-read transform needs whole K-steps)
-        KTimer kt(buf && g.q_scale != nullptr ? "wgemm_tn_dma_aff" : buf ? "wgemm_tn_dma<3, true>" : fast && dma == 4 ? "wgemm_tn_dma<4, false>" : fast && dma == 3 ? "wgemm_tn_dma<3, false>" : fast ? "wgemm_tn<128, 128, 2, 2, true, 16>" : "wgemm_tn<128, 128, 2, 2, false, 16>",
+        KTimer kt(buf && g.q_scale != nullptr ? "wgemm_tn_dma_aff" : buf ? "wgemm_tn_dma<3, true>" : fast ? "wgemm_tn_dma<3, false>" : "wgemm_tn<128, 128, 2, 2, false, 16>",
                   wflops, wbytes, s);
-        if (buf && g.q_scale != nullptr) hipLaunchKernelGGL(wgemm_tn_dma_aff, grid, dim3(256), pad, s, g);
-        else if (buf) hipLaunchKernelGGL((wgemm_tn_dma<3, true>), grid, dim3(256), pad, s, g);
-        else if (fast && dma == 4) hipLaunchKernelGGL((wgemm_tn_dma<4, false>), grid, dim3(256), pad, s, g);
-        else if (fast && dma == 3) hipLaunchKernelGGL((wgemm_tn_dma<3, false>), grid, dim3(256), pad, s, g);
-        else if (fast) hipLaunchKernelGGL((wgemm_tn<128, 128, 2, 2, true>), grid, dim3(256), 0, s, g);
+        if (buf && g.q_scale != nullptr) hipLaunchKernelGGL(wgemm_tn_dma_aff, grid, dim3(256), 0, s, g);
+        else if (buf) hipLaunchKernelGGL((wgemm_tn_dma<3, true>), grid, dim3(256), 0, s, g);
+        else if (fast) hipLaunchKernelGGL((wgemm_tn_dma<3, false>), grid, dim3(256), 0, s, g);
         else hipLaunchKernelGGL((wgemm_tn<128, 128, 2, 2, false>), grid, dim3(256), 0, s, g);
     }
     PDF_LAUNCH_CHECK();
-    if (splits > 1 && g.counters == nullptr && !g.atomic) {
+    if (splits > 1) {
         Reduce r = {ws, out, out1, per, bws, db, db1, (int)perb, splits, accumulate};
         const bool two_d = splits >= 16 && per <= (1L << 20);
         KTimer kt(two_d ? "reduce_slabs_2d" : "reduce_slabs", 0.0, 4.0 * groups * (splits + 1 + (accumulate ? 1 : 0)) * (per + perb), s);

@@ -199,17 +199,12 @@ struct WGemm {
     int rows_per_split;
     int tap_major;                            // tile order: channel-block major, taps inner (same XCD re-reads the same pixels)
     int beta;                                 // single-split launches write dW directly: dW = beta*dW + acc
-    // group 1 of a paired launch (blockIdx.z == 1): P, Q advanced by gsP / gsQ floats, own slab (or output when one split)
+    // group 1 of a paired launch (blockIdx.z == 1): P, Q advanced by gsP / gsQ floats, own slab (or output when one split);
+    // several splits: reduce_slabs sums the slabs in split order
     long gsP, gsQ; float* slab1;
     // optional bias gradient (column sums of P) riding along: per-split partials [split][NI] (or the output itself when one
     // split), accumulated by the j-tile-0 blocks from the P tiles they stage anyway
     float* bslab; float* bslab1;
-    // in-launch reduction of the split slabs (pdf_last_block_arrives): the last block of every output tile sums the slabs in split
-    // order into out / out1 (+= when accumulate) and the bias partials into bout / bout1; counters == NULL: reduce_slabs launch
-    float* out; float* out1; float* bout; float* bout1; int accumulate; int* counters;
-    // atomic != 0 (several splits, accumulate): every block adds its partial tile straight into out / out1 (bout / bout1) with
-    // global_atomic_add_f32 -- no slabs, no reduction pass; the summation order then varies from run to run
-    int atomic;
     const void* P16; const void* Q16;         // bf16 shadows of P / Q (see IGemm::A16)
     const float* q_scale; const float* q_shift;      // Q = relu(Q * q_scale[c] + q_shift[c]) on the fly (see IGemm::a_scale); plain_q only
     // byte extents of P / Q as seen from their (group-adjusted) base pointers, for the buffer descriptors of wgemm_tn_dma<.., true>
@@ -231,37 +226,24 @@ struct WGemm {
 };
 
 
+// a pointer that has the same value in every lane of the wave, as a scalar
+__device__ __forceinline__ float* wave_uniform(float* p) {
+    const unsigned long long a = (unsigned long long)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+    return reinterpret_cast<float*>(((unsigned long long)hi << 32) | lo);
+}
+
 // Epilogue shared by the weight-gradient kernels: this block's partial tile -> its split's slab (or the output itself when there
-// is one split), the bias partial, and -- in-launch -- the reduction over the splits by the tile's last-arriving block.
+// is one split) and the bias partial; reduce_slabs (gemm.hip) sums the splits.
 // bias_thread: this thread carries the bias partial `bval` of output row i0 + threadIdx.x.
 template <int TM, int TN>
 __device__ __forceinline__ void wgemm_finish(const WGemm& g, const f32x16 (&acc)[TM][TN], int i0, int j0, int wm, int wn, int lane,
-                                             bool bias_thread, float bval, int tile_id, int ntiles, int* lds_flag, bool rows_whole = false,
-                                             int split_ = -1, int plane_ = 0) {
+                                             bool bias_thread, float bval, bool rows_whole = false, int split_ = -1, int plane_ = 0) {
     // (split_ >= 0: the caller decoded split / plane from a linear grid, WGemm::bsplits)
-    const int grp = g.batch > 0 ? 0 : blockIdx.z, split = split_ >= 0 ? split_ : (int)blockIdx.y, splits = split_ >= 0 ? g.bsplits : (int)gridDim.y;
+    const int grp = g.batch > 0 ? 0 : blockIdx.z, split = split_ >= 0 ? split_ : (int)blockIdx.y;
     float* slabp = g.batch > 0 ? g.slab + (long)(split_ >= 0 ? plane_ : (int)blockIdx.z) * g.gsW : (grp ? g.slab1 : g.slab);
     float* bslabp = grp ? g.bslab1 : g.bslab;
     const int NJ = g.T * g.Cq;
-    if (g.atomic) {
-        if (bias_thread) atomicAdd((grp ? g.bout1 : g.bout) + i0 + threadIdx.x, bval);
-        float* dst = grp ? g.out1 : g.out;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int col = j0 + wn * TN * 32 + j * 32 + (lane & 31);
-            if (col >= NJ) continue;
-            const int t = col / g.Cq;
-            const int wcol = g.wt[t] * g.Cq + (col - t * g.Cq);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = i0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    if (row < g.NI) atomicAdd(dst + (long)row * g.ldw + wcol, acc[i][j][r]);
-                }
-        }
-        return;
-    }
     if (bias_thread) {
         float* bo = bslabp + (long)split * g.NI + i0 + threadIdx.x;
         *bo = g.beta ? *bo + bval : bval;
@@ -270,7 +252,9 @@ __device__ __forceinline__ void wgemm_finish(const WGemm& g, const f32x16 (&acc)
     if (g.wbytes != 0 && rows_whole) {
         // every row of the tile is inside the matrix: buffer stores (per-lane offset once per 32x32 block, row offsets as scalar
         // operands, columns past NJ dropped by the range check) -- see lean_epilogue
-        const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, g.wbytes, 0x00020000);
+        // (`out` is the same for every lane; told so, the compiler keeps the descriptor in scalar registers -- left to itself it computes the
+        // slab address with vector instructions and wraps each of the accesses below in a loop over the distinct descriptors of the wave)
+        const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)wave_uniform(out), 0, g.wbytes, 0x00020000);
         const unsigned ldw4 = (unsigned)g.ldw * 4u;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -313,35 +297,6 @@ __device__ __forceinline__ void wgemm_finish(const WGemm& g, const f32x16 (&acc)
             }
     }
     }
-    if (g.counters == nullptr || splits == 1) return;
-    if (!pdf_last_block_arrives(g.counters + grp * ntiles + tile_id, splits, lds_flag, true)) return;
-    float* dst = grp ? g.out1 : g.out;
-    const long per = (long)g.NI * g.ldw;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int col = j0 + wn * TN * 32 + j * 32 + (lane & 31);
-        if (col >= NJ) continue;
-        const int t = col / g.Cq;
-        const int wcol = g.wt[t] * g.Cq + (col - t * g.Cq);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = i0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row < g.NI) {
-                    const long pos = (long)row * g.ldw + wcol;
-                    float sum = g.accumulate ? dst[pos] : 0.f;
-                    for (int z = 0; z < splits; ++z) sum += slabp[z * per + pos];
-                    dst[pos] = sum;
-                }
-            }
-    }
-    if (bslabp != nullptr && j0 == 0 && threadIdx.x < TM * 64 && i0 + (int)threadIdx.x < g.NI) {      // TM * 64 = BI rows of this tile
-        float* bdst = grp ? g.bout1 : g.bout;
-        float sum = g.accumulate ? bdst[i0 + threadIdx.x] : 0.f;
-        for (int z = 0; z < splits; ++z) sum += bslabp[(long)z * g.NI + i0 + threadIdx.x];
-        bdst[i0 + threadIdx.x] = sum;
-    }
 }
 
 // Per-kernel timing for bench.py's roofline (pdf_debug_kernel_timing, gemm.hip): while enabled, every GEMM-family kernel launch
@@ -359,7 +314,6 @@ struct KTimer {
 int launch_igemm_bf16(const IGemm& g, hipStream_t s, int groups);
 int igemm_bf16_tile_rows(const IGemm& g, int groups);
 int launch_wgemm_bf16(const WGemm& g, int splits, int groups, int small, hipStream_t s);
-// LDS-DMA form of the fp32 implicit GEMM (gemm_dma.hip).  tile: 64 (64x64) | 128 (128x128) | 12864 | 64128; variant: ring depth / K-step
-// choice; splits > 0: split-K launch (g.ksteps / g.part set).  -> 1 launched, 0 shape not taken.
-int launch_igemm_dma(const IGemm& g, int tile, int variant, int groups, int splits, hipStream_t s);
+// LDS-DMA form of it (gemm_dma.hip).  tile: 64 (64x64) | 128 (128x128) | 12864 (128x64); variant: ring depth / K-step choice.
+// -> 1 launched, 0 shape not taken.
 int launch_igemm_bf16_dma(const IGemm& g, int tile, int variant, int groups, hipStream_t s);

@@ -17,6 +17,7 @@
 // Both kernels: LDS-DMA ring (buffer_load_dwordx4 ... lds, gemm_dma.hip), one [rows][4 chunks] (NT) or [k][columns] (TN) image per
 // component, conflict-free fragment reads by XOR-swizzling WHICH global chunk a DMA lane fetches.
 #include "gemm_common.h"
+#include "gemm_internal.h"
 #include <cstdio>
 
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
@@ -376,10 +377,7 @@ __global__ __launch_bounds__(WM * WN * 64) void x3gemm_nt(const X3Gemm g) {
 // per flop on the 256 x 128 tile (p5 forward, N = 16,384: 0.76 : 0.84; p3 backward-data 0.66 : 0.72) and short reductions are prologue-bound and
 // prefer its fewer blocks (256 -> 256 at 64x64: 0.245 : 0.267) -- as long as those still fill the chip twice over
 static int x3_nt_variant(long M, long N, long K, long batch) {
-    static const int rule = getenv("PDF_X3_TILE_RULE") ? atoi(getenv("PDF_X3_TILE_RULE")) : 2;      // (A/B switch: 0 = round-6 first rule, 1 = K >= 512 -> 8-wave 128 x 128)
     const bool fills = (long)cdiv(M, 256) * cdiv(N, 128) * batch >= 512;
-    if (rule == 0) return fills ? 0 : 1;
-    if (rule == 1) return K >= 512 ? 5 : (fills ? 0 : 5);
     if (N <= 256 && K >= 1024) return 5;
     return fills ? 0 : 5;
 }
@@ -430,7 +428,6 @@ PDF_API int pdf_debug_x3_stamps(unsigned long long* out) {
     (void)out; return 0;
 #endif
 }
-int pdf_internal_batched_gemm(const float* A, const float* B, float* C, int batch, long gsA, long gsB, long gsC, int M, int N, int K, hipStream_t s);
 // the native fp32-MFMA batched product (gemm.hip) behind the same shape of call: the comparison arm of tools/x3_bench.py
 PDF_API int pdf_batched_gemm_nt(const float* A, const float* B, float* C, int batch, long gsA, long gsB, long gsC, int M, int N, int K, void* stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -667,16 +664,12 @@ static int x3_launch_tn(const X3Gemm& g, int nprod, hipStream_t s) {
     return 0;
 }
 
-// the transposed convolutions' weight gradients: tile of the TN kernel (PDF_X3_TN_DECONV: 0 = 128 x 128 on 4 waves, 3 = on 8 waves, 2 = 256 x 128 on 8 waves;
-// default: the wide tile when it still makes >= 256 blocks, else 128 x 128 on 8 waves -- isolated p5 0.77 -> 0.63 ms, p3 0.78 -> 0.70, p4 0.38 -> 0.37; the
-// step does not notice, these run beside the main chain: profiles/r06_tn_deconv.txt)
+// the transposed convolutions' weight gradients: tile of the TN kernel -- 256 x 128 on 8 waves when it still makes >= 256 blocks, else 128 x 128 on
+// 8 waves (against 128 x 128 on 4 waves, isolated: p5 0.77 -> 0.63 ms, p3 0.78 -> 0.70, p4 0.38 -> 0.37; the step does not notice, these run beside the
+// main chain: profiles/r06_tn_deconv.txt)
 static int x3_launch_tn_deconv(const X3Gemm& g, hipStream_t s) {
-    static const int env = getenv("PDF_X3_TN_DECONV") ? atoi(getenv("PDF_X3_TN_DECONV")) : -1;
-    int v = env;
-    if (v < 0) v = (g.M % 256 == 0 && (long)(g.M / 256) * cdiv(g.N, 128) * g.splits * g.batch >= 256) ? 2 : 3;
-    if (v == 3) return x3_launch_tn<2, 4, 2, 1, 3>(g, 6, s);
-    if (v == 2 && g.M % 256 == 0) return x3_launch_tn<4, 2, 2, 2, 2>(g, 6, s);
-    return x3_launch_tn<2, 2, 2, 2, 3>(g, 6, s);
+    if (g.M % 256 == 0 && (long)(g.M / 256) * cdiv(g.N, 128) * g.splits * g.batch >= 256) return x3_launch_tn<4, 2, 2, 2, 2>(g, 6, s);
+    return x3_launch_tn<2, 4, 2, 1, 3>(g, 6, s);
 }
 // rows of the reduction per split and the split count actually used (rows per split a multiple of 32)
 int pdf_internal_x3_tn_splits(int M, int splits) {
@@ -709,7 +702,6 @@ PDF_API int pdf_x3_batched_gemm_tn(const void* P3, long csP, const void* Q3, lon
     const int rc = pdf_internal_x3_batched_wgemm(P3, csP, Q3, csQ, slab, batch, gsP, gsQ, M, NI, NJ, splits, variant, nprod, s);
     return rc > 0 ? 0 : (rc == 0 ? PDF_E_BADARG : rc);
 }
-int pdf_internal_batched_wgemm(const float* P, const float* Q, float* slab, int batch, long gsP, long gsQ, int M, int NI, int NJ, int splits, hipStream_t s);
 // the native fp32 weight-gradient-shaped batched product (gemm.hip; rows per split a multiple of 16)
 PDF_API int pdf_batched_gemm_tn(const float* P, const float* Q, float* slab, int batch, long gsP, long gsQ, int M, int NI, int NJ, int splits, void* stream) {
     hipStream_t s = (hipStream_t)stream;

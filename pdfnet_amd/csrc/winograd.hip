@@ -17,9 +17,8 @@
 // Backward-data is the same convolution of dy with the taps mirrored and the channel roles swapped: only the weight transform differs
 // (U'[xi][ci][co] from w[co][2 - ky][2 - kx][ci]).
 #include "common.h"
+#include "gemm_internal.h"
 #include <cstdio>
-
-int pdf_internal_batched_gemm(const float* A, const float* B, float* C, int batch, long gsA, long gsB, long gsC, int M, int N, int K, hipStream_t s);
 
 // ---- weights: w [Cout][3][3][Cin] -> U [16][N][K]; forward: N = Cout, K = Cin; backward-data (FLIP): N = Cin, K = Cout, taps mirrored
 template <bool FLIP>
@@ -395,21 +394,11 @@ __global__ __launch_bounds__(256) void wino4_wgrad_out_kernel(const float* __res
         }
     }
 }
-int pdf_internal_batched_wgemm(const float* P, const float* Q, float* slab, int batch, long gsP, long gsQ, int M, int NI, int NJ, int splits, hipStream_t s);
-int pdf_internal_x3_batched_gemm(const void* A3, long csA, const void* B3, long csB, float* C, int batch, long gsA, long gsB, long gsC,
-                                 int M, int N, int K, int variant, int nprod, hipStream_t s);
-int pdf_internal_x3_batched_wgemm(const void* P3, long csP, const void* Q3, long csQ, float* slab, int batch, long gsP, long gsQ,
-                                  int M, int NI, int NJ, int splits, int variant, int nprod, hipStream_t s);
 // x3 arithmetic for the F(4x4) transform-domain products (gemm_x3.hip): the transforms write their outputs as x3 planes (6 bytes per element
 // instead of 4) and the 36 products run on the bf16 matrix pipe, six MFMAs per fp32 product.  Whether a transformed tensor [36][T][C] is x3
 // depends on (T, C) ONLY, so every launch that reads it -- the forward that made V, a head sharing it, the weight gradient -- agrees:
 // C % 32 == 0 (a K-step of the products) and the three components within 32-bit byte offsets.  PDF_X3=0 / pdf_set_x3_mode(0): the native fp32 MFMA.
-int pdf_internal_x3_mode();                                  // gemm_x3.hip: bit 0 = these products (PDF_X3, pdf_set_x3_mode)
 static int x3_mode() { return pdf_internal_x3_mode() & 1; }
-static int x3_nprod() {
-    static const int v = getenv("PDF_X3_NPROD") ? atoi(getenv("PDF_X3_NPROD")) : 6;
-    return v;
-}
 static int x3_minc() {
     static const int v = getenv("PDF_X3_MINC") ? atoi(getenv("PDF_X3_MINC")) : 256;
     return v;
@@ -425,8 +414,6 @@ static long x3_mint() {
 static bool wino_x3(long T, int C) { return x3_mode() != 0 && C >= x3_minc() && T >= x3_mint() && C % 32 == 0 && T % 32 == 0 && 73.0 * (double)T * C < 2147483000.0; }
 // a transformed tensor PRIVATE to one launch (backward-data's V of dy; the weight gradient's Yh): its format follows the launch
 static bool wino_x3_fits(long T, int C) { return x3_mode() != 0 && C % 32 == 0 && T % 32 == 0 && 73.0 * (double)T * C < 2147483000.0; }
-int pdf_internal_colsum(const float* g, int ldg, int C, long R, float* out, int accumulate, float* ws, hipStream_t s);
-long pdf_internal_colsum_ws(int C, long R);
 static long wino_minpt();
 static int wino_wgrad_splits(long T, int Co, int Ci) {
     const long tiles = 36L * cdiv(Co, 128) * cdiv(Ci, 128);
@@ -472,7 +459,7 @@ int pdf_internal_conv3x3_winograd_wgrad(const float* x, int ldx, const float* dy
     else hipLaunchKernelGGL((wino4_dy_kernel<false>), dim3(grid_for(T * (Cout / 2), 256, 256 * 32)), dim3(256), 0, s, dy, lddy, Yh, N, H, W, Cout);
     PDF_LAUNCH_CHECK();
     const float* Vq = v_cached != nullptr ? v_cached : V;
-    const int used = x3 ? pdf_internal_x3_batched_wgemm(Yh, 36L * T * Cout, Vq, 36L * T * Cin, slab, 36, T * Cout, T * Cin, (int)T, Cout, Cin, splits, -1, x3_nprod(), s)
+    const int used = x3 ? pdf_internal_x3_batched_wgemm(Yh, 36L * T * Cout, Vq, 36L * T * Cin, slab, 36, T * Cout, T * Cin, (int)T, Cout, Cin, splits, -1, 6, s)
                         : pdf_internal_batched_wgemm(Yh, Vq, slab, 36, T * Cout, T * Cin, (int)T, Cout, Cin, splits, s);
     if (used <= 0) return used < 0 ? used : PDF_E_BADARG;
     if (used > 1) hipLaunchKernelGGL(wino4_slab_sum_kernel, dim3(grid_for(36L * Cout * Cin / 4)), dim3(256), 0, s, slab, used, (long)Cout * Cin / 4);
@@ -563,7 +550,7 @@ int pdf_internal_conv3x3_winograd(const float* x, int ldx, const float* w, const
     }
     PDF_LAUNCH_CHECK();
     if (x3) {
-        if (int rc = pdf_internal_x3_batched_gemm(V, 36L * T * Ck, U, 36L * Cn * Ck, Mx, 36, T * Ck, (long)Cn * Ck, T * Cn, (int)T, Cn, Ck, -1, x3_nprod(), s)) return rc;
+        if (int rc = pdf_internal_x3_batched_gemm(V, 36L * T * Ck, U, 36L * Cn * Ck, Mx, 36, T * Ck, (long)Cn * Ck, T * Cn, (int)T, Cn, Ck, -1, 6, s)) return rc;
     } else if (int rc = pdf_internal_batched_gemm(V, U, Mx, (int)P, T * Ck, (long)Cn * Ck, T * Cn, (int)T, Cn, Ck, s)) return rc;
     if (m == 4) hipLaunchKernelGGL(wino4_output_kernel, dim3(grid_for(T * (Cn / 2), 256, 256 * 32)), dim3(256), 0, s, Mx, bias, y, ldy, N, H, W, Cn, act, accum);
     else hipLaunchKernelGGL(wino_output_kernel, dim3(grid_for(T * (Cn / 4), 256, 256 * 32)), dim3(256), 0, s, Mx, bias, y, ldy, N, H, W, Cn, act, accum);

@@ -42,7 +42,7 @@ def load(d, counter, by_tile=False):
         if by_tile:
             fam = tile_name(k)
         else:
-            fam = ("igemm_nt" if ("igemm_nt" in k or "igemm_halo3x3" in k or "small_k_gemm" in k or "igemm_dma" in k) else "wgemm_tn" if "wgemm_tn" in k else
+            fam = ("igemm_nt" if ("igemm_nt" in k or "igemm_halo3x3" in k or "small_k_gemm" in k) else "wgemm_tn" if "wgemm_tn" in k else
                    "reduce_slabs" if ("reduce_slabs" in k or "splitk_finish" in k) else None)
         if fam is None:
             continue
