@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import gold, make_opt, synthetic_model_outputs, tree_to
+from tests.util import aten_dense_terms as _aten_dense, gold, make_opt, synthetic_model_outputs, tree_to
 
 pytestmark = pytest.mark.gpu
 
@@ -66,18 +66,6 @@ def test_loss_gradient_flows_to_every_trained_output():
         assert t.grad is not None and torch.isfinite(t.grad).all() and t.grad.abs().sum() > 0
     # wh / params heads get no loss term in the reference (simplified.py:397-399,613-614)
     assert other['ret']['wh'].grad is None and other['ret']['params'].grad is None
-
-
-def _aten_dense(mask, mask_gt, hms, hms_gt, hm, hm_gt):
-    """The reference's formulas with aten ops (checker): simplified.py:368,374,376,391; losses.py:138-165."""
-    import torch.nn.functional as TF
-    p = torch.clamp(torch.sigmoid(hm), 1e-4, 1 - 1e-4)
-    pos, neg = hm_gt.eq(1).float(), hm_gt.lt(1).float()
-    pl = (torch.log(p) * (1 - p) ** 2 * pos).sum((1, 2, 3))
-    nl = (torch.log(1 - p) * p ** 2 * (1 - hm_gt) ** 4 * neg).sum((1, 2, 3))
-    npos = pos.sum((1, 2, 3))
-    focal = -nl if float(npos.sum()) == 0 else -(pl + nl) / (npos + 1e-3)
-    return TF.smooth_l1_loss(mask, mask_gt), TF.mse_loss(hms, hms_gt), focal
 
 
 @pytest.mark.parametrize("positives", [True, False])

@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from tests.util import gold, T
+from tests.util import face_terms_ref as ref_terms, gold, T
 
 pytestmark = pytest.mark.gpu
 
@@ -793,6 +793,60 @@ def test_depth2pcl_front_end(F):
     assert (c0 == 0).all() and (n0 == 0).all()
 
 
+DEPTH2PCL_TAU = 1e-5
+
+
+def _depth2pcl_reference(depth, hand_mask, K):
+    """One (sample, hand) of the front end for a general 3x3 K: the oracle's float32 candidates, and in float64 the back-projection
+    inv(K) @ [x, y, 1] * d of every pixel and the pixels whose z lies within DEPTH2PCL_TAU of a bound of the z-window (a float32 kernel may
+    put those on either side once z = depth * (third row of inv(K)) . [x, y, 1] carries rounding)."""
+    from oracle import pdfnet_cpu as O
+    _, cand = O.depth_candidates(depth, hand_mask, K)
+    H, W = depth.shape
+    d = np.where((depth > 0.2) & (depth < 2.5) & (hand_mask > 0.5), depth, 0).astype(np.float64).reshape(-1)
+    y, x = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing='ij')
+    pts = (np.linalg.inv(K.astype(np.float64)) @ np.stack((x.reshape(-1), y.reshape(-1), np.ones(H * W)))) * d
+    z = pts[2]
+    mean = z[z != 0].mean()
+    lo, hi = max(0.2, mean - 0.08), min(2.5, mean + 0.08)
+    band = ((np.abs(z - lo) < DEPTH2PCL_TAU) | (np.abs(z - hi) < DEPTH2PCL_TAU)) & (z != 0)
+    return cand, pts.T, band.nonzero()[0]
+
+
+@pytest.mark.parametrize("third_row", [False, True])
+def test_depth2pcl_with_per_sample_general_cameras(F, third_row):
+    """The front end with a camera matrix of its own per sample (rotation, scale, shift: tests.util.general_cameras), where the test above
+    tiles ONE pinhole matrix: `Kmat + b * 9` and all nine cofactors of the 3x3 inverse count.  With an affine K the third row of the inverse
+    is (0, 0, 1) and z = depth exactly.  With a perturbed third row z carries rounding and a pixel within DEPTH2PCL_TAU of a window bound
+    (float64) could fall on either side: the camera seed is chosen such that no (sample, hand) has such a pixel, which is asserted.  So in
+    both cases candidate sets, counts and the wrap-pad multiset must be exact, and every cloud point must be the float64 back-projection
+    inv(K_b) @ [x, y, 1] * d of the pixel the kernel itself chose."""
+    from tests.util import general_cameras
+    g = gold("op_depth2pcl")
+    depth, mask = g["depth"], g["mask"]
+    B, R = 3, depth.shape[0]
+    K = general_cameras(B, R, 12, third_row)
+    dd = dev(T(depth))[None, None].repeat(B, 1, 1, 1)
+    mm = dev(T(mask))[None].repeat(B, 1, 1, 1)
+    valid = dev(torch.ones(B, 2))
+    choose, cloud, count = F.depth2pcl(dd, mm, dev(K), valid, seed=123)
+    ch, cnt = choose.cpu().numpy(), count.cpu().numpy()
+    for b in range(B):
+        for hand, mch in ((0, 1), (1, 0)):                                       # left reads mask channel 1, right channel 0
+            cand, pts64, band = _depth2pcl_reference(depth, mask[mch], K[b].numpy())
+            assert len(cand) >= 10 and len(band) == 0, (b, hand, len(cand), band)
+            sel = ch[b, hand]
+            assert int(cnt[b, hand]) == len(cand), (b, hand, int(cnt[b, hand]), len(cand))
+            if len(cand) <= 1024:                                                # np.pad(..., 'wrap') multiset
+                assert np.array_equal(np.sort(sel), np.sort(np.pad(cand, (0, 1024 - len(cand)), 'wrap'))), (b, hand)
+            else:                                                                # 1024 distinct candidates
+                assert len(np.unique(sel)) == 1024 and np.isin(sel, cand).all(), (b, hand)
+            assert not np.array_equal(sel, np.sort(sel))                         # shuffled
+            close(cloud[b, hand], T(pts64[sel]), 1e-6, rtol=1e-5, what="cloud of sample %d hand %d" % (b, hand))
+    for b0, b1 in ((0, 1), (0, 2), (1, 2)):                                      # same depth and mask, three cameras: three clouds
+        assert float((cloud[b0] - cloud[b1]).abs().max()) > 1e-3
+
+
 def test_paired_decoder_ops(F):
     """The paired / fused launches of the mesh decoder against their one-branch-at-a-time compositions (torch CPU)."""
     from oracle import pdfnet_cpu as O
@@ -902,15 +956,6 @@ def test_mesh_loss_kernels(F):
     pred, gt = rnd(G, B, V, 3, seed=1, scale=0.05), rnd(G, B, V, 3, seed=2, scale=0.05)
     gen = torch.Generator().manual_seed(3)
     faces = torch.stack([torch.stack([torch.randperm(V, generator=gen)[:3] for _ in range(1538)]) for _ in range(G)])
-    unit = lambda v: TF.normalize(v, p=2, dim=2)
-
-    def ref_terms(p, q, fc):
-        f0, f1, f2 = fc[:, 0], fc[:, 1], fc[:, 2]
-        n = unit(torch.cross(unit(q[:, f1] - q[:, f0]), unit(q[:, f2] - q[:, f0]), dim=2))
-        cos = [torch.abs((unit(v) * n).sum(2, keepdim=True)) for v in (p[:, f1] - p[:, f0], p[:, f2] - p[:, f0], p[:, f2] - p[:, f1])]
-        d = lambda x, i, j: torch.sqrt(((x[:, i] - x[:, j]) ** 2).sum(2, keepdim=True))
-        ed = [torch.abs(d(p, i, j) - d(q, i, j)) for i, j in ((f0, f1), (f0, f2), (f1, f2))]
-        return torch.cat(cos, 1).mean(), torch.cat(ed, 1).mean()
     pr = pred.clone().requires_grad_()
     refs = [ref_terms(pr[g], gt[g], faces[g]) for g in range(G)]
     wn, we = torch.tensor([1.5, -0.7]), torch.tensor([0.3, 2.0])

@@ -107,6 +107,57 @@ def synthetic_model_outputs(B, R, seed):
     return result, params, hand, other
 
 
+def general_cameras(B, R, seed, third_row=False):
+    """Per-sample camera matrices [B,3,3] float32 that are NOT the one pinhole matrix of synthetic_train_batch: K[b] = A_b @ K0 with
+    K0 = [[R,0,R/2],[0,R,R/2],[0,0,1]] and A_b a 2-D affine map in homogeneous form drawn per sample -- rotation within +-30 degrees,
+    scale 0.8 .. 1.2, translation within +-0.08 R (what the dataset's rotation / scale augmentation does to K): every entry of the first two
+    rows is non-zero and differs between samples.  third_row=True also perturbs the last row to (e0, e1, 1 + e2), |e0|, |e1| <= 0.01,
+    |e2| <= 0.02: no entry of K is then 0 or 1, and a point at depth ~0.45 still projects with a depth near 0.45."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    ang = g.uniform(-np.pi / 6, np.pi / 6, B)
+    s = g.uniform(0.8, 1.2, B)
+    t = g.uniform(-0.08 * R, 0.08 * R, (B, 2))
+    e = g.uniform(-1.0, 1.0, (B, 3)) * np.array([0.01, 0.01, 0.02])
+    A = np.zeros((B, 3, 3))
+    A[:, 0, 0], A[:, 0, 1], A[:, 0, 2] = s * np.cos(ang), -s * np.sin(ang), t[:, 0]
+    A[:, 1, 0], A[:, 1, 1], A[:, 1, 2] = s * np.sin(ang), s * np.cos(ang), t[:, 1]
+    A[:, 2, 2] = 1.0
+    K = A @ np.array([[R, 0, R / 2], [0, R, R / 2], [0, 0, 1]], np.float64)
+    if third_row:
+        K[:, 2] = e + np.array([0.0, 0.0, 1.0])
+    K = K.astype(np.float32)
+    for b in range(1, B):
+        assert (np.abs(K[b, :2] - K[:b, :2]).min(axis=0) > 0).all()      # every sample's entries are its own
+    assert (K[:, :2] != 0).all()
+    return torch.from_numpy(K)
+
+
+def aten_dense_terms(mask, mask_gt, hms, hms_gt, hm, hm_gt):
+    """The dense-map terms of the reference with aten ops (checker; any float dtype): SmoothL1 on the masks, MSE on the joint heat-maps,
+    CornerNet focal loss [B] on the clamped sigmoid of the centre map (simplified.py:368,374,376,391; losses.py:138-165)."""
+    import torch.nn.functional as TF
+    p = torch.clamp(torch.sigmoid(hm), 1e-4, 1 - 1e-4)
+    pos, neg = hm_gt.eq(1).to(hm.dtype), hm_gt.lt(1).to(hm.dtype)
+    pl = (torch.log(p) * (1 - p) ** 2 * pos).sum((1, 2, 3))
+    nl = (torch.log(1 - p) * p ** 2 * (1 - hm_gt) ** 4 * neg).sum((1, 2, 3))
+    npos = pos.sum((1, 2, 3))
+    focal = -nl if float(npos.sum()) == 0 else -(pl + nl) / (npos + 1e-3)
+    return TF.smooth_l1_loss(mask, mask_gt), TF.mse_loss(hms, hms_gt), focal
+
+
+def face_terms_ref(p, q, fc):
+    """(normal loss, edge-length loss) of lib/trains/simplified.py:66-115 for ONE hand with aten ops (checker; any float dtype):
+    p, q [B,V,3] prediction / ground truth, fc [F,3] int64."""
+    import torch.nn.functional as TF
+    unit = lambda v: TF.normalize(v, p=2, dim=2)
+    f0, f1, f2 = fc[:, 0], fc[:, 1], fc[:, 2]
+    n = unit(torch.cross(unit(q[:, f1] - q[:, f0]), unit(q[:, f2] - q[:, f0]), dim=2))
+    cos = [torch.abs((unit(v) * n).sum(2, keepdim=True)) for v in (p[:, f1] - p[:, f0], p[:, f2] - p[:, f0], p[:, f2] - p[:, f1])]
+    d = lambda x, i, j: torch.sqrt(((x[:, i] - x[:, j]) ** 2).sum(2, keepdim=True))
+    ed = [torch.abs(d(p, i, j) - d(q, i, j)) for i, j in ((f0, f1), (f0, f2), (f1, f2))]
+    return torch.cat(cos, 1).mean(), torch.cat(ed, 1).mean()
+
+
 def tree_to(obj, device):
     if torch.is_tensor(obj):
         return obj.to(device)
