@@ -417,6 +417,20 @@ int pdf_procrustes_dist(const float* pred, const float* gt, int rows, int n, flo
  * thr: T thresholds in metres in HOST memory (read during the call), 1 <= T <= 4.  n <= 1024. */
 int pdf_mesh_nn_counts(const float* pred, const float* gt, int rows, int n, const float* thr, int T, int* counts, float* d_gt, float* d_pred,
                        void* stream);
+/* Inter-hand penetration.  Row (b, h): every vertex of hand h of sample b against the triangle mesh of the OTHER hand of that sample
+ * (vertices verts[b][1-h], triangles faces[1-h]).
+ * verts [B,2,n,3] f32 metres (|coordinate| < 1e6); faces [2,Fc,3] int64, the same tensor pdf_face_loss_fwd takes (left, right); an index outside
+ * [0, n) is clamped into it.
+ *   wind  [B,2,n] or NULL: generalized winding number of the vertex with respect to the other mesh (sum of the triangles' Van Oosterom-Strackee
+ *                          solid angles / 4 pi; +1 inside an outward-oriented closed mesh)
+ *   dist  [B,2,n] or NULL: distance from the vertex to the closest point of the other mesh's surface (vertex, edge and face regions)
+ *   count [B,2] int32: vertices with wind > 0.5 ("inside")
+ *   depth [B,2]: largest dist among the inside vertices, 0 when there is none
+ *   gap   [B,2]: smallest dist over all n vertices
+ * A degenerate triangle adds no solid angle and the distance to its segments; finite input gives finite output.
+ * 1 <= n <= 1024, 1 <= Fc <= 2048, else PDF_E_BADARG with nothing launched; B <= 0 returns 0.  No atomics: two runs are bit-identical. */
+int pdf_mesh_penetration(const float* verts, const long long* faces, int B, int n, int Fc,
+                         float* wind, float* dist, int* count, float* depth, float* gap, void* stream);
 
 /* ---- depth front end (csrc/frontend.hip) ------------------------------------------------------ */
 /* depth2pcl (intaghand_encoder.py:369-491 + get_points_coordinate lib/utils/utils.py:251-262) batched on the GPU:

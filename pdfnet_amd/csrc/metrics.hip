@@ -249,3 +249,121 @@ PDF_API int pdf_mesh_nn_counts(const float* pred, const float* gt, int rows, int
     PDF_LAUNCH_CHECK();
     return 0;
 }
+
+// Inter-hand penetration: every vertex of one hand against the triangle mesh of the other hand of the same sample.  One block per row
+// = (sample, hand); the OTHER hand's vertex planes (12 KB) and its face indices as 16-bit triples (16 KB) are staged in LDS, one lane owns one
+// query vertex and all lanes walk the triangles together, so every LDS read of the loop is a broadcast.  1,024 lanes: the 778 vertices of a
+// hand take one round of 13 waves, 3-4 per SIMD, which hide each other's LDS and atan2f latency (profiles/NOTES.md has the 256-lane form's time).
+// Per triangle, with a, b, c the corners relative to the query:
+//   solid angle  2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|)   (Van Oosterom-Strackee), summed in double, / 4 pi = wind;
+//   distance^2 = the smallest of the three segment distances (parameter clamped to [0, 1]: the vertex and edge regions) and, where the
+//   projection of the query falls inside the triangle (the face region), of the plane distance (a.n)^2 / n.n with n = (b - a) x (c - a).
+// A triangle collapsed to a point has a.(b x c) = 0 and n = 0 exactly: it adds atan2(0, den >= +0) = 0 and the distance to that point.
+// Nothing is divided by a length that can be zero, so finite coordinates (|x| < 1e6: the cubes stay finite) give finite output.
+#define PEN_T 1024
+#define PEN_MAXF 2048
+#define PEN_TINY 1e-37f
+
+// p q - r s from separately rounded products (no fma): a cross product built from it is exactly zero for equal vectors and exactly negated
+// when the two change places
+__device__ __forceinline__ float pen_det2(float p, float q, float r, float s) {
+#pragma clang fp contract(off)
+    return p * q - r * s;
+}
+__device__ __forceinline__ float pen_seg_d2(float px, float py, float pz, float ex, float ey, float ez) {
+    // squared distance from the origin to the segment p + t e, t in [0, 1]
+    const float ee = ex * ex + ey * ey + ez * ez, pe = px * ex + py * ey + pz * ez;
+    const float t = fminf(fmaxf(-pe * __frcp_rn(fmaxf(ee, PEN_TINY)), 0.f), 1.f);
+    const float qx = px + t * ex, qy = py + t * ey, qz = pz + t * ez;
+    return qx * qx + qy * qy + qz * qz;
+}
+
+__global__ __launch_bounds__(PEN_T) void mesh_penetration_kernel(const float* __restrict__ verts, const long long* __restrict__ faces, int n, int Fc,
+                                                                 float* __restrict__ wind, float* __restrict__ dist, int* __restrict__ count,
+                                                                 float* __restrict__ depth, float* __restrict__ gap) {
+    __shared__ float ox[MET_MAXN], oy[MET_MAXN], oz[MET_MAXN];
+    __shared__ ushort4 tri[PEN_MAXF];
+    __shared__ int red_c[PEN_T / 64];
+    __shared__ float red_d[PEN_T / 64], red_g[PEN_T / 64];
+    const long row = blockIdx.x;
+    const int h = (int)(row & 1);
+    const float* other = verts + (row ^ 1) * n * 3;            // rows 2b, 2b + 1 are the two hands of sample b
+    for (int e = threadIdx.x; e < 3 * n; e += PEN_T) {
+        const int i = e / 3, k = e - 3 * i;
+        (k == 0 ? ox : k == 1 ? oy : oz)[i] = other[e];
+    }
+    const long long* fo = faces + (long)(1 - h) * Fc * 3;
+    for (int t = threadIdx.x; t < Fc; t += PEN_T) {
+        ushort4 f;                                             // an index outside [0, n) is clamped: it must not leave the staged planes
+        f.x = (unsigned short)min(max(fo[3 * t + 0], 0LL), (long long)(n - 1));
+        f.y = (unsigned short)min(max(fo[3 * t + 1], 0LL), (long long)(n - 1));
+        f.z = (unsigned short)min(max(fo[3 * t + 2], 0LL), (long long)(n - 1));
+        f.w = 0;
+        tri[t] = f;
+    }
+    __syncthreads();
+    int cnt = 0;
+    float dep = 0.f, gp = 3.0e38f;
+    for (int i = threadIdx.x; i < n; i += PEN_T) {
+        const float* p = verts + (row * n + i) * 3;
+        const float x = p[0], y = p[1], z = p[2];
+        double omega = 0.0;
+        float best = 3.0e38f;
+        for (int t = 0; t < Fc; ++t) {
+            const ushort4 f = tri[t];
+            const float ax = ox[f.x] - x, ay = oy[f.x] - y, az = oz[f.x] - z;
+            const float bx = ox[f.y] - x, by = oy[f.y] - y, bz = oz[f.y] - z;
+            const float cx = ox[f.z] - x, cy = oy[f.z] - y, cz = oz[f.z] - z;
+            const float la = sqrtf(ax * ax + ay * ay + az * az), lb = sqrtf(bx * bx + by * by + bz * bz), lc = sqrtf(cx * cx + cy * cy + cz * cz);
+            const float ab = ax * bx + ay * by + az * bz, bc = bx * cx + by * cy + bz * cz, ca = cx * ax + cy * ay + cz * az;
+            const float ux = pen_det2(by, cz, bz, cy), uy = pen_det2(bz, cx, bx, cz), uz = pen_det2(bx, cy, by, cx);      // b x c
+            const float det = ax * ux + ay * uy + az * uz;
+            const float den = la * lb * lc + ab * lc + bc * la + ca * lb;
+            omega += (double)atan2f(det, den);
+            // edges e1 = b - a, e2 = c - a; d1 .. d6 of the region test: e1.(-a), e2.(-a), e1.(-b), e2.(-b), e1.(-c), e2.(-c)
+            const float e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
+            float d2 = fminf(fminf(pen_seg_d2(ax, ay, az, e1x, e1y, e1z), pen_seg_d2(ax, ay, az, e2x, e2y, e2z)),
+                             pen_seg_d2(bx, by, bz, cx - bx, cy - by, cz - bz));
+            const float d1 = -(e1x * ax + e1y * ay + e1z * az), d2a = -(e2x * ax + e2y * ay + e2z * az);
+            const float d3 = -(e1x * bx + e1y * by + e1z * bz), d4 = -(e2x * bx + e2y * by + e2z * bz);
+            const float d5 = -(e1x * cx + e1y * cy + e1z * cz), d6 = -(e2x * cx + e2y * cy + e2z * cz);
+            const float vc = d1 * d4 - d3 * d2a, vb = d5 * d2a - d1 * d6, va = d3 * d6 - d5 * d4;
+            const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+            const float nn = nx * nx + ny * ny + nz * nz;
+            // (a sliver whose corner angle is below 1e-5 rad has a normal made of rounding noise: its segments are the triangle)
+            const float e11 = e1x * e1x + e1y * e1y + e1z * e1z, e22 = e2x * e2x + e2y * e2y + e2z * e2z;
+            if (va >= 0.f && vb >= 0.f && vc >= 0.f && nn > fmaxf(1e-10f * e11 * e22, PEN_TINY)) {
+                const float an = ax * nx + ay * ny + az * nz;
+                d2 = fminf(d2, an * an * __frcp_rn(nn));
+            }
+            best = fminf(best, d2);
+        }
+        const float w = (float)(omega * (2.0 / (4.0 * 3.14159265358979323846))), d = sqrtf(best);
+        if (wind != nullptr) wind[row * n + i] = w;
+        if (dist != nullptr) dist[row * n + i] = d;
+        gp = fminf(gp, d);
+        if (w > 0.5f) { ++cnt; dep = fmaxf(dep, d); }
+    }
+    // count: an integer sum; depth / gap: a maximum / minimum.  None depends on the order, which is fixed anyway.
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    cnt = wave_sum_i(cnt);
+    dep = wave_max(dep);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gp = fminf(gp, __shfl_xor(gp, o, 64));
+    if (lane == 0) { red_c[wave] = cnt; red_d[wave] = dep; red_g[wave] = gp; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < PEN_T / 64; ++k) { cnt += red_c[k]; dep = fmaxf(dep, red_d[k]); gp = fminf(gp, red_g[k]); }
+        count[row] = cnt; depth[row] = dep; gap[row] = gp;
+    }
+}
+PDF_API int pdf_mesh_penetration(const float* verts, const long long* faces, int B, int n, int Fc, float* wind, float* dist, int* count,
+                                 float* depth, float* gap, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (n < 1 || n > MET_MAXN || Fc < 1 || Fc > PEN_MAXF || verts == nullptr || faces == nullptr || count == nullptr || depth == nullptr || gap == nullptr)
+        return PDF_E_BADARG;
+    hipLaunchKernelGGL(mesh_penetration_kernel, dim3(2 * B), dim3(PEN_T), 0, s, verts, faces, n, Fc, wind, dist, count, depth, gap);
+    PDF_LAUNCH_CHECK();
+    return 0;
+}

@@ -2430,6 +2430,26 @@ def mesh_nn_counts(pred, gt, thresholds, return_dist=False):
     return (counts, d_gt, d_pred) if return_dist else counts
 
 
+def mesh_penetration(verts, faces, return_fields=False):
+    """verts [..., 2, n, 3] (left, right hand), faces [2, Fc, 3] int64 (left, right: the loss module's `faces_pair`) -> per hand, its vertices
+    against the OTHER hand's mesh: (count int32 [..., 2] of vertices whose generalized winding number exceeds 0.5, depth [..., 2] = the largest
+    distance to the other surface among them (0 without any), gap [..., 2] = the smallest distance of any vertex to the other surface).
+    return_fields: also (wind, dist) [..., 2, n].  n <= 1024, Fc <= 2048 (csrc/metrics.hip stages a mesh in LDS).  No gradient."""
+    hip.require_gpu(verts, faces)
+    v, f = verts.detach().float().contiguous(), faces.detach().long().contiguous()
+    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
+        raise ValueError("pdfnet_amd: mesh_penetration wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
+    n, Fc = v.shape[-2], f.shape[1]
+    if not (1 <= n <= 1024 and 1 <= Fc <= 2048):
+        raise ValueError("pdfnet_amd: mesh_penetration takes 1 to 1024 vertices and 1 to 2048 faces per hand, got %d and %d" % (n, Fc))
+    lead = v.shape[:-2]
+    count = torch.empty(lead, dtype=torch.int32, device=v.device)
+    depth, gap = (torch.empty(lead, dtype=torch.float32, device=v.device) for _ in range(2))
+    wind, dist = (torch.empty(v.shape[:-1], dtype=torch.float32, device=v.device) for _ in range(2)) if return_fields else (None, None)
+    _L().pdf_mesh_penetration(ptr(v), ptr(f), count.numel() // 2, n, Fc, ptr(wind), ptr(dist), ptr(count), ptr(depth), ptr(gap), stream())
+    return (count, depth, gap, wind, dist) if return_fields else (count, depth, gap)
+
+
 # ----------------------------------------------------------------------------------------------
 # Fused mesh decoder (csrc/meshdec.hip, round 5): one DualGraphLayer (DualGraph.py:62-92) = three launches forward, see the kernel file.
 MESH_FUSED = _os.environ.get("PDFNET_MESH_FUSED", "1") != "0"

@@ -622,7 +622,7 @@ class Trainer:
         return tot / max(n, 1)
 
 
-    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False):
+    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False):
         """Counterpart of `BaseTrainer.evaluation` (lib/trains/base_trainer.py:207-429, H2O branch): the test-mode pass
         (centres from the predicted heat-map, root from the predicted depth) and the mean Euclidean errors per hand --
         absolute and root-relative joints / vertices in mm, 2-D landmarks in pixels.  The reference evaluates on rank 0
@@ -637,7 +637,11 @@ class Trainer:
         aligned:    also the figures the hand-mesh literature compares on (the reference carries their arithmetic in lib/utils/eval.py and
                     eval_util.py but never reaches it, base_trainer.py:396-398): Procrustes-aligned MPJPE / MPVPE, mesh F-scores at
                     5 / 15 mm and the AUC of the aligned joints' PCK curve -- the keys of `finish_aligned`, from a second device
-                    accumulator that travels with the first (still one all-reduce, one host sync).  The other keys do not change."""
+                    accumulator that travels with the first (still one all-reduce, one host sync).  The other keys do not change.
+        interaction: also how the two hands sit relative to each other, over the samples with both hands valid: the relative-root position
+                    error (MRRPE) and the penetration / contact figures of `finish_interaction` (`F.mesh_penetration`: every vertex of a hand
+                    against the other hand's mesh), for the prediction and for the ground truth.  A third accumulator in the same buffer;
+                    needs the loss module's `faces_pair`.  The other keys do not change."""
         mwl = self.model_with_loss
         was_training = mwl.training
         mwl.eval()
@@ -649,6 +653,8 @@ class Trainer:
             if aligned:
                 acc2 = torch.zeros(8, dtype=torch.float64, device=dev)    # PA sums and F-score sums, see aligned_sums
                 pck = torch.zeros((21, PCK_STEPS), dtype=torch.int64, device=dev)
+            if interaction:
+                acc3 = torch.zeros(12, dtype=torch.float64, device=dev)   # see interaction_sums
             poses = []
             with torch.no_grad():
                 for batch in loader:
@@ -659,6 +665,8 @@ class Trainer:
                         sums, table = aligned_sums(tup)
                         acc2 += sums
                         pck += table
+                    if interaction:
+                        acc3 += interaction_sums(tup, batch, mwl.loss.faces_pair)
                     if json_path is not None:
                         if 'id' not in batch or 'frame_num' not in batch:
                             raise KeyError("Trainer.evaluation: hand_poses.json needs batch['id'] and batch['frame_num'] (interhand.py H2O entries)")
@@ -668,12 +676,16 @@ class Trainer:
                         poses.append(torch.cat((key, jp.reshape(jp.shape[0], -1).double()), 1))          # [B, 2 + 126]
             if aligned:                                            # one buffer for the reduction and the copy (the counts are exact in float64)
                 acc = torch.cat((acc, acc2, pck.reshape(-1).double()))
+            if interaction:
+                acc = torch.cat((acc, acc3))
             if self.world > 1:
                 dist.all_reduce(acc)
             acc = acc.cpu()
             out = finish_evaluation(acc[:11])
             if aligned:
-                out.update(finish_aligned(acc[11:19], acc[19:].reshape(21, PCK_STEPS).round().long(), out['samples']))
+                out.update(finish_aligned(acc[11:19], acc[19:19 + 21 * PCK_STEPS].reshape(21, PCK_STEPS).round().long(), out['samples']))
+            if interaction:
+                out.update(finish_interaction(acc[-12:]))
             if json_path is not None:
                 rows = torch.cat(poses) if poses else torch.zeros((0, 128), dtype=torch.float64, device=dev)
                 if self.world > 1:                                 # ragged gather: pad every rank's block to the longest
@@ -807,6 +819,54 @@ def write_aligned_scores(path, ev):
     with open(path, 'a') as fo:
         fo.write('eval aligned \n')
         for k in ALIGNED_KEYS:
+            fo.write('%s: %.2f\n' % (k, ev[k]))
+
+
+INTERACTION_KEYS = ('mrrpe_mm', 'pen_ratio_left', 'pen_ratio_right', 'pen_ratio', 'pen_depth_mm', 'pen_rate', 'contact_mm',
+                    'gt_pen_ratio', 'gt_pen_depth_mm', 'gt_pen_rate', 'gt_contact_mm', 'interaction_samples')
+
+
+def interaction_sums(tup, batch, faces):
+    """test-mode 9-tuple, the batch (its `valid` [B, 2]) and the faces [2, Fc, 3] (left, right) -> float64 [12] on the device, sums over the
+    samples whose two hands are both valid: [0] their number; [1] ||(root_R - root_L)_pred - (root_R - root_L)_gt|| with root = absolute minus
+    root-relative joint 0; then five terms of `F.mesh_penetration` for the predicted absolute vertices [2:7] and the same five for the
+    ground-truth vertices [7:12]: inside share count / n of the left hand's vertices (inside the right mesh), of the right hand's, the deeper of
+    the two penetration depths, 1 if any vertex of either hand is inside, the smaller of the two gaps (metres)."""
+    vp, jp, vg, jg, _, _, jpo, _, jgo = tup
+    both = (batch['valid'][:, 0] == 1) & (batch['valid'][:, 1] == 1)                             # [B]
+    root_p, root_g = (jp - jpo)[:, :, 0].double(), (jg - jgo)[:, :, 0].double()                  # [B, 2, 3]
+    rel = ((root_p[:, 1] - root_p[:, 0]) - (root_g[:, 1] - root_g[:, 0])).norm(dim=-1)
+    parts = [torch.ones_like(rel), rel]
+    for v in (vp, vg):
+        count, depth, gap = F.mesh_penetration(v, faces)
+        share = count.double() / v.shape[-2]
+        parts += [share[:, 0], share[:, 1], depth.double().amax(1), (count.sum(1) > 0).double(), gap.double().amin(1)]
+    terms = torch.stack(parts)                                                                   # [12, B]
+    return torch.where(both, terms, torch.zeros_like(terms)).sum(1)
+
+
+def finish_interaction(acc):
+    """The accumulator of `interaction_sums` -> means over the two-handed samples: 'mrrpe_mm'; 'pen_ratio_left' / '_right' (share of that
+    hand's vertices inside the other hand's mesh) and their mean 'pen_ratio'; 'pen_depth_mm' (the deepest inside vertex's distance to the other
+    surface); 'pen_rate' (share of samples with any vertex inside); 'contact_mm' (smallest vertex-to-surface distance between the hands); the
+    same for the ground-truth meshes as 'gt_*' (the data's own level of contact); 'interaction_samples'.  Only the last one without a sample."""
+    n = float(acc[0])
+    out = {'interaction_samples': int(round(n))}
+    if out['interaction_samples'] == 0:
+        return out
+    m = [float(x) / n for x in acc]
+    res = {'mrrpe_mm': m[1] * 1000, 'pen_ratio_left': m[2], 'pen_ratio_right': m[3], 'pen_ratio': (m[2] + m[3]) / 2, 'pen_depth_mm': m[4] * 1000,
+           'pen_rate': m[5], 'contact_mm': m[6] * 1000, 'gt_pen_ratio': (m[7] + m[8]) / 2, 'gt_pen_depth_mm': m[9] * 1000, 'gt_pen_rate': m[10],
+           'gt_contact_mm': m[11] * 1000}
+    res.update(out)
+    return {k: res[k] for k in INTERACTION_KEYS}
+
+
+def write_interaction_scores(path, ev):
+    """Append the figures of `evaluation(interaction=True)` as a block of their own (`key: %.2f`, like `write_aligned_scores`)."""
+    with open(path, 'a') as fo:
+        fo.write('eval interaction \n')
+        for k in INTERACTION_KEYS:
             fo.write('%s: %.2f\n' % (k, ev[k]))
 
 
