@@ -432,6 +432,37 @@ int pdf_mesh_nn_counts(const float* pred, const float* gt, int rows, int n, cons
 int pdf_mesh_penetration(const float* verts, const long long* faces, int B, int n, int Fc,
                          float* wind, float* dist, int* count, float* depth, float* gap, void* stream);
 
+/* ---- hand renderer (csrc/render.hip) ------------------------------------------------------------ */
+/* Forward-only z-buffered rasteriser of both hands of every sample under that sample's pinhole camera (the reference's pytorch3d
+ * MeshRasterizer + HardPhongShader, lib/models/networks/mano_utils.py:44-156).  The arithmetic contract -- pixel (i, j) sampled at
+ * (u, v) = (j + 0.5, i + 0.5) with u = K00 X / Z + K02, v = K11 Y / Z + K12; coverage by edge functions evaluated from the lower to the higher
+ * vertex index; perspective-correct depth and barycentrics; smallest depth wins, then the lower face index; Phong constants -- is the header
+ * comment of csrc/render.hip.
+ * verts [B,2,n,3] f32 camera-space metres (left, right); faces [2,Fc,3] int64, the tensor pdf_mesh_penetration takes (an index outside [0, n) is
+ * clamped); K [B,3,3] f32; valid [B,2] f32 or NULL (0 = that hand is not drawn).  Face ids of the output: 0 .. Fc-1 left, Fc .. 2Fc-1 right.
+ * A face is skipped whole when its hand is not valid, when a vertex has Z < z_near (z_near > 0), or when its screen area is exactly 0.
+ *   face  [B,H,W] int32: the visible face, -1 for background
+ *   depth [B,H,W] f32: its Z at the pixel centre, 0 for background
+ *   bary  [B,H,W,3] f32 or NULL: perspective-correct barycentrics of the pixel centre in that face, 0 for background
+ *   rgb   [B,H,W,3] f32 or NULL: Phong-shaded vertex colours (ambient_only != 0: the interpolated colour itself), 0 for background.  Needs
+ *         colour [2,n,3] (colour_per_sample == 0) or [B,2,n,3] f32, and, unless ambient_only, table [2,n,M] int32: the faces (0 .. Fc-1 of that
+ *         hand) incident to each vertex, padded with -1 -- the vertex normals are gathered over it.  Without them: PDF_E_BADARG.
+ * scratch: 16 * B * n floats, 16-byte aligned (per vertex: screen x, y, 1/Z, Z and the normal); overwritten by every call.
+ * 1 <= n <= 1024, 1 <= Fc <= 2048, 1 <= H, W <= 2048, 1 <= M <= 32 (pass 1 without a table), B <= 65535, else PDF_E_BADARG with nothing
+ * launched; B <= 0 returns 0.  No atomics: two runs are bit-identical. */
+int pdf_render_hands(const float* verts, const long long* faces, const float* K, const float* valid, const float* colour, int colour_per_sample,
+                     const int* table, int B, int n, int Fc, int M, int H, int W, float z_near, int ambient_only, float* scratch,
+                     int* face, float* depth, float* bary, float* rgb, void* stream);
+/* Two renders and a sensor depth map compared in the image plane, per sample.
+ * face_pred, face_gt [B,H,W] int32 (pdf_render_hands of the prediction and of the ground truth), depth_pred [B,H,W] the prediction's depth,
+ * sensor [B,H,W] f32 metres (0 or less = no measurement) or NULL.
+ *   iou [B,2,2] int32: per hand (face ids [h Fc, (h+1) Fc)) the pixels where it is visible in both maps, and in either
+ *   res [B,2] f32 or NULL: (sum of |depth_pred - sensor|, number of pixels) over the pixels with a predicted surface and sensor > 0; needs
+ *       depth_pred; (0, 0) without a sensor map
+ * 1 <= Fc <= 2048, 1 <= H, W <= 2048, else PDF_E_BADARG with nothing launched; B <= 0 returns 0.  Fixed-order reduction, no atomics. */
+int pdf_render_compare(const int* face_pred, const int* face_gt, const float* depth_pred, const float* sensor, int B, int H, int W, int Fc,
+                       int* iou, float* res, void* stream);
+
 /* ---- depth front end (csrc/frontend.hip) ------------------------------------------------------ */
 /* depth2pcl (intaghand_encoder.py:369-491 + get_points_coordinate lib/utils/utils.py:251-262) batched on the GPU:
  * depth [B][H][W] metres, mask [B][2][H][W] (right, left), K [B][3][3], valid [B][2] ->

@@ -2451,6 +2451,117 @@ def mesh_penetration(verts, faces, return_fields=False):
 
 
 # ----------------------------------------------------------------------------------------------
+# Hand renderer (csrc/render.hip): the reference's pytorch3d MeshRasterizer + HardPhongShader (mano_utils.py:44-156) as a tile rasteriser.
+RENDER_MAX_DEGREE = 32
+
+
+def vertex_face_table(faces, n=None):
+    """faces [2, Fc, 3] (left, right) -> int32 [2, n, M] on faces' device: per hand and vertex the faces (0 .. Fc-1, ascending) that contain it,
+    padded with -1; M = the largest number of faces at a vertex (at most 32).  n defaults to the largest index + 1.  Built on the host (one
+    copy of `faces` to it): build it once per topology and hand it to `render_hands`."""
+    f = faces.detach().long().cpu()
+    if f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3 or f.shape[1] < 1:
+        raise ValueError("pdfnet_amd: vertex_face_table wants faces [2, Fc, 3], got %s" % (tuple(f.shape),))
+    n = int(f.max()) + 1 if n is None else int(n)
+    if int(f.min()) < 0 or int(f.max()) >= n:
+        raise ValueError("pdfnet_amd: vertex_face_table: face indices must lie in [0, %d)" % n)
+    rows = [[[] for _ in range(n)] for _ in range(2)]
+    for h in range(2):
+        for k, tri in enumerate(f[h].tolist()):
+            for v in sorted(set(tri)):
+                rows[h][v].append(k)
+    M = max(1, max(len(r) for hand in rows for r in hand))
+    if M > RENDER_MAX_DEGREE:
+        raise ValueError("pdfnet_amd: vertex_face_table: a vertex belongs to %d faces, at most %d are supported" % (M, RENDER_MAX_DEGREE))
+    table = torch.tensor([[r + [-1] * (M - len(r)) for r in hand] for hand in rows], dtype=torch.int32)
+    return table.to(faces.device)
+
+
+def render_hands(verts, faces, K, size, valid=None, colour=None, table=None, ambient_only=False, z_near=0.01, return_bary=False):
+    """verts [..., 2, n, 3] camera-space metres (left, right hand), faces [2, Fc, 3] int64 (the loss module's `faces_pair`), K [..., 3, 3],
+    size = (H, W) -> (face int32 [..., H, W]: the visible face, 0 .. Fc-1 left, Fc .. 2Fc-1 right, -1 background; depth [..., H, W]: its Z,
+    0 background [; bary [..., H, W, 3] with return_bary] [; rgb [..., H, W, 3] with colour]).
+    valid [..., 2]: a hand with 0 is not drawn.  colour [2, n, 3] or [..., 2, n, 3]: vertex colours, shaded with pytorch3d's HardPhongShader
+    defaults (point light at (0, 0, -1), ambient 0.5, diffuse 0.3, specular 0.2, shininess 64) or, with ambient_only, interpolated as they
+    are.  table: `vertex_face_table(faces, n)` for the vertex normals; built here (on the host) when it is needed and missing.  A face with a
+    vertex nearer than z_near is skipped.  The arithmetic contract is the header comment of csrc/render.hip.  n <= 1024, Fc <= 2048,
+    H, W <= 2048.  No gradient; deterministic."""
+    hip.require_gpu(verts, faces, K, valid, colour, table)
+    v, f, k = verts.detach().float().contiguous(), faces.detach().long().contiguous(), K.detach().float().contiguous()
+    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
+        raise ValueError("pdfnet_amd: render_hands wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
+    lead, n, Fc = v.shape[:-3], v.shape[-2], f.shape[1]
+    if k.shape != lead + (3, 3):
+        raise ValueError("pdfnet_amd: render_hands wants K %s for verts %s, got %s" % (tuple(lead) + (3, 3), tuple(v.shape), tuple(k.shape)))
+    try:
+        H, W = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise ValueError("pdfnet_amd: render_hands wants size = (H, W), got %r" % (size,))
+    if not (1 <= n <= 1024 and 1 <= Fc <= 2048 and 1 <= H <= 2048 and 1 <= W <= 2048):
+        raise ValueError("pdfnet_amd: render_hands takes 1 to 1024 vertices and 1 to 2048 faces per hand and images of 1 to 2048 pixels a side, "
+                         "got n = %d, Fc = %d, size = (%d, %d)" % (n, Fc, H, W))
+    if not z_near > 0:
+        raise ValueError("pdfnet_amd: render_hands wants z_near > 0, got %r" % (z_near,))
+    B = v.numel() // (2 * n * 3)
+    if B > 65535:
+        raise ValueError("pdfnet_amd: render_hands takes at most 65535 samples a call, got %d" % B)
+    va = None
+    if valid is not None:
+        va = valid.detach().float().contiguous()
+        if va.shape != lead + (2,):
+            raise ValueError("pdfnet_amd: render_hands wants valid %s, got %s" % (tuple(lead) + (2,), tuple(va.shape)))
+    col, per_sample, M = None, 0, 1
+    if colour is not None:
+        col = colour.detach().float().contiguous()
+        if col.shape not in ((2, n, 3), tuple(v.shape)):
+            raise ValueError("pdfnet_amd: render_hands wants colour [2, %d, 3] or %s, got %s" % (n, tuple(v.shape), tuple(col.shape)))
+        per_sample = int(col.dim() > 3)
+        if not ambient_only:
+            if table is None:
+                table = vertex_face_table(f, n)
+            table = table.detach().int().contiguous()
+            if table.dim() != 3 or table.shape[:2] != (2, n) or not 1 <= table.shape[2] <= RENDER_MAX_DEGREE:
+                raise ValueError("pdfnet_amd: render_hands wants table [2, %d, 1..%d] (vertex_face_table), got %s" % (n, RENDER_MAX_DEGREE, tuple(table.shape)))
+            M = table.shape[2]
+        else:
+            table = None
+    else:
+        table = None
+    dev = v.device
+    face = torch.empty(lead + (H, W), dtype=torch.int32, device=dev)
+    depth = torch.empty(lead + (H, W), dtype=torch.float32, device=dev)
+    bary = torch.empty(lead + (H, W, 3), dtype=torch.float32, device=dev) if return_bary else None
+    rgb = torch.empty(lead + (H, W, 3), dtype=torch.float32, device=dev) if col is not None else None
+    scratch = torch.empty(max(B, 1) * n * 16, dtype=torch.float32, device=dev)
+    _L().pdf_render_hands(ptr(v), ptr(f), ptr(k), ptr(va), ptr(col), per_sample, ptr(table), B, n, Fc, M, H, W, float(z_near), int(bool(ambient_only)),
+                          ptr(scratch), ptr(face), ptr(depth), ptr(bary), ptr(rgb), stream())
+    return tuple(x for x in (face, depth, bary, rgb) if x is not None)
+
+
+def render_compare(face_pred, face_gt, depth_pred, Fc, sensor=None):
+    """Two face maps of `render_hands` [..., H, W] int32 (prediction, ground truth), the prediction's depth map and optionally a sensor depth map
+    [..., H, W] (metres, <= 0 = no measurement) -> (iou int32 [..., 2, 2]: per hand (left, right) the number of pixels where it is the visible
+    surface in both maps and in either; res [..., 2]: (sum of |depth_pred - sensor|, number of pixels) over the pixels with a predicted surface
+    and a measurement, zeros without a sensor map).  Fc: faces per hand.  No gradient; deterministic."""
+    hip.require_gpu(face_pred, face_gt, depth_pred, sensor)
+    if face_pred.dtype != torch.int32 or face_gt.dtype != torch.int32:
+        raise ValueError("pdfnet_amd: render_compare wants int32 face maps, got %s and %s" % (face_pred.dtype, face_gt.dtype))
+    fp, fg, dp = face_pred.contiguous(), face_gt.contiguous(), depth_pred.detach().float().contiguous()
+    if fp.dim() < 2 or fg.shape != fp.shape or dp.shape != fp.shape or (sensor is not None and sensor.shape != fp.shape):
+        raise ValueError("pdfnet_amd: render_compare wants maps of one shape [..., H, W], got %s, %s, %s%s" % (
+            tuple(fp.shape), tuple(fg.shape), tuple(dp.shape), "" if sensor is None else ", %s" % (tuple(sensor.shape),)))
+    H, W = fp.shape[-2:]
+    if not (1 <= int(Fc) <= 2048 and 1 <= H <= 2048 and 1 <= W <= 2048):
+        raise ValueError("pdfnet_amd: render_compare takes 1 to 2048 faces per hand and images of 1 to 2048 pixels a side, got Fc = %d, size = (%d, %d)" % (Fc, H, W))
+    sd = sensor.detach().float().contiguous() if sensor is not None else None
+    lead = fp.shape[:-2]
+    iou = torch.empty(lead + (2, 2), dtype=torch.int32, device=fp.device)
+    res = torch.empty(lead + (2,), dtype=torch.float32, device=fp.device)
+    _L().pdf_render_compare(ptr(fp), ptr(fg), ptr(dp), ptr(sd), iou.numel() // 4, H, W, int(Fc), ptr(iou), ptr(res), stream())
+    return iou, res
+
+
+# ----------------------------------------------------------------------------------------------
 # Fused mesh decoder (csrc/meshdec.hip, round 5): one DualGraphLayer (DualGraph.py:62-92) = three launches forward, see the kernel file.
 MESH_FUSED = _os.environ.get("PDFNET_MESH_FUSED", "1") != "0"
 # bf16 mode: the mesh decoder stays on the fused fp32 kernels (its products are latency-bound, not MFMA-bound: 1 % of the step's FLOPs; the

@@ -622,7 +622,7 @@ class Trainer:
         return tot / max(n, 1)
 
 
-    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False):
+    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False, rendered=False):
         """Counterpart of `BaseTrainer.evaluation` (lib/trains/base_trainer.py:207-429, H2O branch): the test-mode pass
         (centres from the predicted heat-map, root from the predicted depth) and the mean Euclidean errors per hand --
         absolute and root-relative joints / vertices in mm, 2-D landmarks in pixels.  The reference evaluates on rank 0
@@ -641,7 +641,11 @@ class Trainer:
         interaction: also how the two hands sit relative to each other, over the samples with both hands valid: the relative-root position
                     error (MRRPE) and the penetration / contact figures of `finish_interaction` (`F.mesh_penetration`: every vertex of a hand
                     against the other hand's mesh), for the prediction and for the ground truth.  A third accumulator in the same buffer;
-                    needs the loss module's `faces_pair`.  The other keys do not change."""
+                    needs the loss module's `faces_pair`.  The other keys do not change.
+        rendered:   also the agreement in the image plane: the predicted and the ground-truth absolute meshes are rendered under
+                    batch['K_new'] at the input's resolution (`F.render_hands`) and compared (`F.render_compare`): silhouette IoU per hand, and the
+                    mean |rendered Z - sensor Z| over the pixels the prediction covers when the batch carries its `depth` map -- the keys of
+                    `finish_rendered`.  One more accumulator in the same buffer; needs `faces_pair`.  The other keys do not change."""
         mwl = self.model_with_loss
         was_training = mwl.training
         mwl.eval()
@@ -655,6 +659,8 @@ class Trainer:
                 pck = torch.zeros((21, PCK_STEPS), dtype=torch.int64, device=dev)
             if interaction:
                 acc3 = torch.zeros(12, dtype=torch.float64, device=dev)   # see interaction_sums
+            if rendered:
+                acc4 = torch.zeros(8, dtype=torch.float64, device=dev)    # see rendered_sums
             poses = []
             with torch.no_grad():
                 for batch in loader:
@@ -667,6 +673,8 @@ class Trainer:
                         pck += table
                     if interaction:
                         acc3 += interaction_sums(tup, batch, mwl.loss.faces_pair)
+                    if rendered:
+                        acc4 += rendered_sums(tup, batch, mwl.loss.faces_pair)
                     if json_path is not None:
                         if 'id' not in batch or 'frame_num' not in batch:
                             raise KeyError("Trainer.evaluation: hand_poses.json needs batch['id'] and batch['frame_num'] (interhand.py H2O entries)")
@@ -676,6 +684,9 @@ class Trainer:
                         poses.append(torch.cat((key, jp.reshape(jp.shape[0], -1).double()), 1))          # [B, 2 + 126]
             if aligned:                                            # one buffer for the reduction and the copy (the counts are exact in float64)
                 acc = torch.cat((acc, acc2, pck.reshape(-1).double()))
+            if rendered:                                           # before the interaction block, which is read from the end
+                at = acc.numel()
+                acc = torch.cat((acc, acc4))
             if interaction:
                 acc = torch.cat((acc, acc3))
             if self.world > 1:
@@ -686,6 +697,8 @@ class Trainer:
                 out.update(finish_aligned(acc[11:19], acc[19:19 + 21 * PCK_STEPS].reshape(21, PCK_STEPS).round().long(), out['samples']))
             if interaction:
                 out.update(finish_interaction(acc[-12:]))
+            if rendered:
+                out.update(finish_rendered(acc[at:at + 8]))
             if json_path is not None:
                 rows = torch.cat(poses) if poses else torch.zeros((0, 128), dtype=torch.float64, device=dev)
                 if self.world > 1:                                 # ragged gather: pad every rank's block to the longest
@@ -868,6 +881,60 @@ def write_interaction_scores(path, ev):
         fo.write('eval interaction \n')
         for k in INTERACTION_KEYS:
             fo.write('%s: %.2f\n' % (k, ev[k]))
+
+
+RENDERED_KEYS = ('sil_iou_left', 'sil_iou_right', 'sil_iou', 'depth_res_mm', 'rendered_samples')
+
+
+def rendered_sums(tup, batch, faces):
+    """test-mode 9-tuple, the batch (`K_new` [B, 3, 3], `valid` [B, 2], `input` [B, C, H, W] for the resolution, optionally the sensor's `depth`
+    [B, 1, H, W] in metres) and the faces [2, Fc, 3] -> float64 [8] on the device: [0] the number of samples; the predicted and the ground-truth
+    absolute vertices are rendered at H x W (`F.render_hands`, a hand with valid = 0 is not drawn) and compared (`F.render_compare`): [1:3] the
+    sum of intersection / union of the left (right) hand's visible pixels over the samples with that hand valid and a non-empty union, [3:5]
+    the number of such samples; [5] the sum of |rendered Z - sensor Z| over the pixels with a predicted surface and sensor depth > 0, [6]
+    their number, [7] the number of samples that came with a `depth` map (all three 0 without one)."""
+    vp, vg = tup[0], tup[2]
+    H, W = batch['input'].shape[-2:]
+    valid = batch['valid']
+    fp, dp = F.render_hands(vp, faces, batch['K_new'], (H, W), valid=valid)
+    fg, _ = F.render_hands(vg, faces, batch['K_new'], (H, W), valid=valid)
+    sensor = batch.get('depth')
+    if sensor is not None:
+        if sensor.numel() != fp.numel():
+            raise ValueError("rendered_sums: batch['depth'] %s is no [B, 1, %d, %d] map" % (tuple(sensor.shape), H, W))
+        sensor = sensor.reshape(fp.shape)
+    iou, res = F.render_compare(fp, fg, dp, faces.shape[1], sensor)
+    inter, union = iou[..., 0].double(), iou[..., 1].double()                                    # [B, 2]
+    has = (valid == 1) & (union > 0)
+    ratio = torch.where(has, inter / union.clamp(min=1), torch.zeros_like(union))
+    n = torch.full((1,), float(vp.shape[0]), dtype=torch.float64, device=vp.device)
+    return torch.cat((n, ratio.sum(0), has.double().sum(0), res.double().sum(0), n if sensor is not None else torch.zeros_like(n)))
+
+
+def finish_rendered(acc):
+    """The accumulator of `rendered_sums` -> 'sil_iou_left' / 'sil_iou_right' (mean silhouette IoU of that hand over the samples that have it
+    valid and visible in either render; absent without such a sample), 'sil_iou' (mean of the two, or the one there is), 'depth_res_mm' (mean
+    |rendered Z - sensor Z| per pixel that the prediction covers and the sensor measured, 0 if there is no such pixel; absent when no batch
+    carried a `depth` map), 'rendered_samples'."""
+    out = {}
+    for i, k in ((1, 'sil_iou_left'), (2, 'sil_iou_right')):
+        if round(float(acc[i + 2])) > 0:
+            out[k] = float(acc[i]) / float(acc[i + 2])
+    if out:
+        out['sil_iou'] = sum(out.values()) / len(out)
+    if round(float(acc[7])) > 0:
+        out['depth_res_mm'] = float(acc[5]) / max(float(acc[6]), 1.0) * 1000
+    out['rendered_samples'] = int(round(float(acc[0])))
+    return out
+
+
+def write_rendered_scores(path, ev):
+    """Append the figures of `evaluation(rendered=True)` that are there as a block of their own (`key: %.2f`, like `write_aligned_scores`)."""
+    with open(path, 'a') as fo:
+        fo.write('eval rendered \n')
+        for k in RENDERED_KEYS:
+            if k in ev:
+                fo.write('%s: %.2f\n' % (k, ev[k]))
 
 
 def write_hand_poses_json(path, rows):
