@@ -37,9 +37,8 @@ int pdf_linear_fwd(const float* x, const float* w, const float* bias, float* y,
 int pdf_linear_bwd_weight(const float* x, const float* dy, float* dw, float* db, float* ws, long ws_floats,
                           int M, int N, int K, int ldx, int lddy, int accumulate, void* stream);
 long pdf_wgrad_workspace_floats(int M, int NI, int NJ);
-/* Allocates the library's ticket-counter ring (csrc/common.h pdf_last_block_arrives: in-launch finalisation of BatchNorm
- * statistics and weight-gradient slabs).  Called once per process after the device is selected, outside any stream capture;
- * the entry points call it lazily otherwise. */
+/* Allocates the library's process-wide rings (csrc/common.h: the split-K scratch ring, the event ring).  Called once per
+ * process after the device is selected, outside any stream capture; the entry points call it lazily otherwise. */
 int pdf_init(void);
 /* The device the rings were created on (-1 before pdf_init).  One process drives one GPU: pdf_init from another current
  * device returns PDF_E_WORKSPACE. */

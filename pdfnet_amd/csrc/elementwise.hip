@@ -563,27 +563,8 @@ PDF_API int pdf_adam_step(float* p, const float* g, float* m, float* v, long n, 
 
 
 // ---------------------------------------------------------------------------------------------
-// ticket-counter ring of common.h (pdf_last_block_arrives)
 #include <atomic>
 #include <mutex>
-int* pdf_ticket_counters(int n) {
-    static int* base = nullptr;
-    static std::once_flag once;
-    static std::atomic<long> next{0};
-    std::call_once(once, [] {
-        if (hipMalloc(&base, sizeof(int) * PDF_COUNTER_RING) != hipSuccess) { base = nullptr; return; }
-        if (hipMemset(base, 0, sizeof(int) * PDF_COUNTER_RING) != hipSuccess || hipDeviceSynchronize() != hipSuccess) base = nullptr;
-    });
-    if (base == nullptr || n <= 0 || n > PDF_COUNTER_RING) return nullptr;
-    long o = next.fetch_add(n);
-    long start = o % PDF_COUNTER_RING;
-    if (start + n > PDF_COUNTER_RING) {                      // do not straddle the end: take the region at the start of the ring instead
-        o = next.fetch_add(n + (PDF_COUNTER_RING - start)) + (PDF_COUNTER_RING - start);
-        start = o % PDF_COUNTER_RING;
-        if (start + n > PDF_COUNTER_RING) start = 0;
-    }
-    return base + start;
-}
 // split-K scratch ring of common.h (pdf_scratch)
 float* pdf_scratch(long floats) {
     static float* base = nullptr;
@@ -732,7 +713,7 @@ PDF_API int pdf_stream_create(void** out, int priority, int* lo, int* hi) {
     return 0;
 }
 
-// The rings (ticket counters, split-K scratch, events) are process-wide and live on the device that was current at the first
+// The rings (split-K scratch, events) are process-wide and live on the device that was current at the first
 // call: one process drives one GPU (one rank per GPU).  A later call from another current device is refused instead of handing
 // kernels on GPU n the memory and events of GPU m.
 static std::atomic<int> g_init_device{-1};
@@ -743,5 +724,5 @@ PDF_API int pdf_init(void) {
     int expected = -1;
     if (!g_init_device.compare_exchange_strong(expected, dev) && expected != dev) return PDF_E_WORKSPACE;
     if (int rc = pdf_event_ring()) return rc;
-    return (pdf_ticket_counters(1) != nullptr && pdf_scratch(64) != nullptr) ? 0 : PDF_E_WORKSPACE;
+    return pdf_scratch(64) != nullptr ? 0 : PDF_E_WORKSPACE;
 }

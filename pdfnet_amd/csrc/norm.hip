@@ -8,32 +8,111 @@
 // ---------------------------------------------------------------------------------------------
 // BatchNorm2d / BatchNorm1d over rows.  Statistics are accumulated as shifted sums
 // sum(x - x0), sum((x - x0)^2) (x0 = first row) in fp32 per thread, combined in fp64.
+//
+// Every column pass (reduction or streaming) is ONE body in two instantiations over V, the channels a thread owns: a block is
+// 64 channels = BN_TX(V) = 64 / V channel groups x BN_TY(V) = 256 / BN_TX(V) row lanes.
+//   V = 4: 16 channel quads x 16 row lanes, 16-byte accesses, 4 rows in flight per thread (the scalar form moved 1.1-1.6 TB/s:
+//          one 4-byte load in flight per thread)
+//   V = 1: 64 channels x 4 row lanes -- C % 4 != 0, an odd leading dimension or an unaligned pointer (v4_ok)
+// A block walks its own contiguous chunk of rows_per_chunk rows: rows r0 + ty, r0 + ty + BN_TY, ...
 #define BN_CT 64   // channels per block
-__global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ x, int ldx, int C, long R, long rows_per_chunk,
-                                                         float* __restrict__ part /*[chunks][C][2]*/) {
-    __shared__ float s1[4][BN_CT], s2[4][BN_CT];
-    const int tx = threadIdx.x & (BN_CT - 1), ty = threadIdx.x / BN_CT;
-    const int c = blockIdx.x * BN_CT + tx;
-    const long r0 = blockIdx.y * rows_per_chunk;
-    const long r1 = min(R, r0 + rows_per_chunk);
-    float a = 0.f, b = 0.f;
-    if (c < C) {
-        const float sh = x[c];
-        for (long r = r0 + ty; r < r1; r += 4) {
-            float v = x[r * ldx + c] - sh;
-            a += v; b += v * v;
-        }
-    }
-    s1[ty][tx] = a; s2[ty][tx] = b;
-    __syncthreads();
-    if (ty == 0 && c < C) {
-        a = s1[0][tx] + s1[1][tx] + s1[2][tx] + s1[3][tx];
-        b = s2[0][tx] + s2[1][tx] + s2[2][tx] + s2[3][tx];
-        part[((long)blockIdx.y * C + c) * 2 + 0] = a;
-        part[((long)blockIdx.y * C + c) * 2 + 1] = b;
+#define BN_TX(V) (BN_CT / (V))
+#define BN_TY(V) (256 / BN_TX(V))
+template <int V> using vf = float __attribute__((ext_vector_type(V)));      // V floats, component-wise arithmetic, 4 V bytes aligned
+template <int V> __device__ __forceinline__ vf<V> vld(const float* p) { return *reinterpret_cast<const vf<V>*>(p); }
+template <int V> __device__ __forceinline__ void vst(float* p, vf<V> v) { *reinterpret_cast<vf<V>*>(p) = v; }
+template <int V> __device__ __forceinline__ vf<V> vfma(vf<V> a, vf<V> b, vf<V> c) {
+    vf<V> r;
+#pragma unroll
+    for (int i = 0; i < V; ++i) r[i] = fmaf(a[i], b[i], c[i]);
+    return r;
+}
+__device__ __forceinline__ float add_rounded_product(float acc, float p, float q) {                // acc + p * q, never fused
+#pragma clang fp contract(off)
+    const float pq = p * q;
+    return acc + pq;
+}
+__device__ __forceinline__ float sum_of_rounded_products(float a, float b, float c, float d) {      // a * b + c * d, never fused
+#pragma clang fp contract(off)
+    const float ab = a * b, cd = c * d;
+    return ab + cd;
+}
+// acc + p * q in a running sum.  The two forms have always rounded this differently: the float4 kernels fuse it, the scalar kernels
+// round the product first (the compiler paired their two accumulators into one packed add before it could contract).  Each keeps
+// its rounding, spelled out here so that it no longer depends on what the compiler makes of the loop.
+template <int V> __device__ __forceinline__ vf<V> bn_acc(vf<V> acc, vf<V> p, vf<V> q) {
+    if constexpr (V == 1) { vf<1> r; r[0] = add_rounded_product(acc[0], p[0], q[0]); return r; }
+    else return vfma<V>(p, q, acc);
+}
+template <int V> __device__ __forceinline__ vf<V> vrsqrt_eps(vf<V> var, float eps) {
+    vf<V> r;
+#pragma unroll
+    for (int i = 0; i < V; ++i) r[i] = 1.f / sqrtf(var[i] + eps);
+    return r;
+}
+__device__ __forceinline__ void vst_bf16(unsigned short* p, vf<4> v) {     // the bf16 shadow of four floats: one 8-byte store
+    *reinterpret_cast<uint2*>(p) = uint2{pdf_pk_bf16(v[0], v[1]), pdf_pk_bf16(v[2], v[3])};
+}
+__device__ __forceinline__ vf<4> as_vf(float4 v) { return vf<4>{v.x, v.y, v.z, v.w}; }
+// bf16 storage mode: the BatchNorm input x (a conv output nobody else reads) may come as bf16 (X16): 4 channels = one 8-byte load
+template <int V, bool X16>
+__device__ __forceinline__ vf<V> ld_x(const float* __restrict__ x, long idx) {
+    if constexpr (X16) {
+        static_assert(V == 4, "bf16 input: float4 form only");
+        const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(x) + idx);
+        return vf<4>{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
+    } else {
+        return vld<V>(x + idx);
     }
 }
+// the row lanes of a block summed in lane order 0, 1, ... -> part[blockIdx.y][c0 .. c0 + V)[2]  (two == false: the second sum is 0)
+template <int V>
+__device__ __forceinline__ void bn_block_reduce(vf<V> a, vf<V> b, vf<V> (&sa)[BN_TY(V)][BN_TX(V)], vf<V> (&sb)[BN_TY(V)][BN_TX(V)],
+                                                float* __restrict__ part, int C, int c0, bool two) {
+    const int tx = threadIdx.x & (BN_TX(V) - 1), ty = threadIdx.x / BN_TX(V);
+    sa[ty][tx] = a;
+    if (two) sb[ty][tx] = b;
+    __syncthreads();
+    if (ty == 0 && c0 < C) {
+        vf<V> x = sa[0][tx], y = {};
+        if (two) y = sb[0][tx];
+        for (int j = 1; j < BN_TY(V); ++j) { x += sa[j][tx]; if (two) y += sb[j][tx]; }
+        float* o = part + ((long)blockIdx.y * C + c0) * 2;
+#pragma unroll
+        for (int i = 0; i < V; ++i) { o[2 * i] = x[i]; o[2 * i + 1] = two ? y[i] : 0.f; }
+    }
+}
+// g = dy under the ReLU of the forward.  relu 0: none; 1: mask from the saved output y; 2: no residual went into the ReLU, so its
+// mask is recomputed from x as fmaf(x, scale, shift) > 0 -- the exact expression of the forward -- and y is not read at all
+template <int V>
+__device__ __forceinline__ vf<V> bn_masked_grad(vf<V> g, int relu, const float* __restrict__ y_at, vf<V> xv, vf<V> sc, vf<V> sh) {
+    if (relu) {
+        const vf<V> yv = relu == 2 ? vfma<V>(xv, sc, sh) : vld<V>(y_at);
+#pragma unroll
+        for (int i = 0; i < V; ++i) if (!(yv[i] > 0.f)) g[i] = 0.f;
+    }
+    return g;
+}
 
+template <int V, bool X16>
+__global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ x, int ldx, int C, long R, long rows_per_chunk,
+                                                         float* __restrict__ part /*[chunks][C][2]*/, float* __restrict__ shift0) {
+    __shared__ vf<V> sa[BN_TY(V)][BN_TX(V)], sb[BN_TY(V)][BN_TX(V)];
+    const int tx = threadIdx.x & (BN_TX(V) - 1), ty = threadIdx.x / BN_TX(V);
+    const int c0 = blockIdx.x * BN_CT + tx * V;
+    const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
+    vf<V> a = {}, b = {};
+    if (c0 < C) {
+        const vf<V> sh = ld_x<V, X16>(x, c0);
+        if (X16 && blockIdx.y == 0 && ty == 0) vst<V>(shift0 + c0, sh);      // (the finaliser's `x[c]`: row 0 as floats)
+#pragma unroll 4
+        for (long r = r0 + ty; r < r1; r += BN_TY(V)) {
+            const vf<V> v = ld_x<V, X16>(x, r * ldx + c0) - sh;
+            a += v; b = bn_acc<V>(b, v, v);
+        }
+    }
+    bn_block_reduce<V>(a, b, sa, sb, part, C, c0, true);
+}
 
 // sum the per-chunk partials part[chunk][C][2] for channel c: 64 channels x 16 chunk-lanes per block
 // (a serial 512-iteration loop per channel was latency-bound: ~50 us for a kernel that moves a few KB)
@@ -54,76 +133,34 @@ __device__ __forceinline__ void reduce_chunks(const float* __restrict__ part, in
     for (int j = 0; j < FIN_TY; ++j) { a += s1[j][tx]; b += s2[j][tx]; }
 }
 
-static bool bn_inlaunch(int C, long R) {
-    static long maxb = -2;
-    if (maxb == -2) { const char* e = getenv("PDF_BN_INLAUNCH_MAXMB"); maxb = e ? atol(e) : 0; }
-    return maxb < 0 || (long)C * R * 4 <= maxb * (1L << 20);
-}
-
-// ---- finalize inside the partial kernels (pdf_last_block_arrives): the last block of a 64-channel tile sums the chunk
-// partials part[chunk][C][2] in a fixed order -- 64 channels x 4 chunk lanes, doubles -- and writes the per-channel results.
-// Saves one launch per BatchNorm call (164 per step) but every block then waits for its write-through stores and the ticket
-// before it retires, and the tile's last block adds the serial sum: measured on MI355X the partial kernels run 1.3-1.4 ms
-// per step longer than the finalize launches they replace (fp32 B=32 393 vs 399 img/s, bf16 652 vs 664), so it is opt-in:
-// PDF_BN_INLAUNCH_MAXMB=<n> enables it for tensors up to n MiB (-1: always).
-__device__ __forceinline__ bool tile_sums(const float* __restrict__ part, int chunks, int C, int c_tile, double* red /*[2][4][64]*/, double& a, double& b) {
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int c = c_tile * BN_CT + tx;
-    a = 0.0; b = 0.0;
-    if (c < C) {
-        const float2* p2 = reinterpret_cast<const float2*>(part) + c;
-        for (int k = ty; k < chunks; k += 4) { const float2 v = p2[(long)k * C]; a += v.x; b += v.y; }
-    }
-    red[ty * 64 + tx] = a; red[256 + ty * 64 + tx] = b;
-    __syncthreads();
-    a = (red[tx] + red[64 + tx]) + (red[128 + tx] + red[192 + tx]);
-    b = (red[256 + tx] + red[320 + tx]) + (red[384 + tx] + red[448 + tx]);
-    return ty == 0 && c < C;
-}
-struct BnFin {                                              // forward finalize arguments
+// what the statistics of channel c turn into: save_mean / save_rstd for the backward, the running statistics, and the
+// coefficients scale / shift of the apply pass.  `var` is the biased variance over R rows.
+struct BnFin {
     const float* gamma; const float* beta; float* running_mean; float* running_var; float momentum, eps;
-    float* save_mean; float* save_rstd; float* scale; float* shift; int* counters;
-    float* shift0;                                          // X16 input: row 0 of x as floats (written by the partial kernel)
+    float* save_mean; float* save_rstd; float* scale; float* shift;
 };
-__device__ __forceinline__ void bn_finalize_tile(const float* __restrict__ part, int chunks, const float* __restrict__ x, int C, long R, const BnFin& f,
-                                                 int c_tile, double* red) {
-    double a, b;
-    if (!tile_sums(part, chunks, C, c_tile, red, a, b)) return;
-    const int c = c_tile * BN_CT + (threadIdx.x & 63);
-    const double n = (double)R;
-    const double dm = a / n;
-    double var = b / n - dm * dm;
+__device__ __forceinline__ void bn_finish_channel(int c, double mean, double var, long R, const BnFin& f) {
     if (var < 0.0) var = 0.0;
-    const double mean = dm + (double)x[c];
+    const double n = (double)R;
     const float rstd = (float)(1.0 / sqrt(var + (double)f.eps));
     f.save_mean[c] = (float)mean;
     f.save_rstd[c] = rstd;
+    // (roundings spelled out -- two rounded products and a rounded sum for the running statistics, one fused step for shift -- so
+    // that they do not depend on whether the compiler pairs the two products into one packed multiply or contracts one of them)
     if (f.running_mean != nullptr) {
-        f.running_mean[c] = (1.f - f.momentum) * f.running_mean[c] + f.momentum * (float)mean;
+        const float keep = 1.f - f.momentum;
+        f.running_mean[c] = sum_of_rounded_products(keep, f.running_mean[c], f.momentum, (float)mean);
         const double unb = R > 1 ? var * n / (n - 1.0) : var;
-        f.running_var[c] = (1.f - f.momentum) * f.running_var[c] + f.momentum * (float)unb;
+        f.running_var[c] = sum_of_rounded_products(keep, f.running_var[c], f.momentum, (float)unb);
     }
     const float sc = f.gamma[c] * rstd;
     f.scale[c] = sc;
-    f.shift[c] = f.beta[c] - (float)mean * sc;
-}
-struct BnBwdFin { const float* gamma; const float* rstd; float* dgamma; float* dbeta; int accumulate; float* coef; int* counters; };
-__device__ __forceinline__ void bn_bwd_finalize_tile(const float* __restrict__ part, int chunks, int C, long R, const BnBwdFin& f, int c_tile, double* red) {
-    double a, b;
-    if (!tile_sums(part, chunks, C, c_tile, red, a, b)) return;
-    const int c = c_tile * BN_CT + (threadIdx.x & 63);
-    if (f.accumulate) { f.dbeta[c] += (float)a; f.dgamma[c] += (float)b; }
-    else { f.dbeta[c] = (float)a; f.dgamma[c] = (float)b; }
-    f.coef[c] = f.gamma[c] * f.rstd[c];
-    f.coef[C + c] = (float)(a / (double)R);
-    f.coef[2 * C + c] = (float)(b / (double)R);
+    f.shift[c] = fmaf(-(float)mean, sc, f.beta[c]);
 }
 
-__global__ __launch_bounds__(FIN_TX * FIN_TY) void bn_finalize_kernel(const float* __restrict__ part, int chunks, const float* __restrict__ x, int C, long R,
-                                   const float* __restrict__ gamma, const float* __restrict__ beta,
-                                   float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps,
-                                   float* __restrict__ save_mean, float* __restrict__ save_rstd,
-                                   float* __restrict__ scale, float* __restrict__ shift) {
+// x0: the row the partial kernel shifted by (row 0 of x; of a bf16 x, its copy as floats)
+__global__ __launch_bounds__(FIN_TX * FIN_TY) void bn_finalize_kernel(const float* __restrict__ part, int chunks, const float* __restrict__ x0, int C, long R,
+                                                                      const BnFin f) {
     __shared__ double s1[FIN_TY][FIN_TX], s2[FIN_TY][FIN_TX];
     const int c = blockIdx.x * FIN_TX + threadIdx.x;
     double a, b;
@@ -131,20 +168,7 @@ __global__ __launch_bounds__(FIN_TX * FIN_TY) void bn_finalize_kernel(const floa
     if (c >= C || threadIdx.y != 0) return;
     const double n = (double)R;
     const double dm = a / n;
-    double var = b / n - dm * dm;
-    if (var < 0.0) var = 0.0;
-    const double mean = dm + (double)x[c];
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    save_mean[c] = (float)mean;
-    save_rstd[c] = rstd;
-    if (running_mean != nullptr) {
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-        const double unb = R > 1 ? var * n / (n - 1.0) : var;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
-    const float sc = gamma[c] * rstd;
-    scale[c] = sc;
-    shift[c] = beta[c] - (float)mean * sc;
+    bn_finish_channel(c, dm + (double)x0[c], b / n - dm * dm, R, f);
 }
 
 // Statistics that arrive as per-row-block (mean, M2) pairs out of the producing GEMM's epilogue (IGemm::stat, gemm_common.h):
@@ -152,11 +176,7 @@ __global__ __launch_bounds__(FIN_TX * FIN_TY) void bn_finalize_kernel(const floa
 // (deterministic): mean = sum n_t mean_t / R, M2 = sum (M2_t + n_t mean_t^2) - R mean^2.
 #define FT_C 16                                              // channels per block
 #define FT_L 64                                              // tile lanes per channel
-__global__ __launch_bounds__(FT_C * FT_L) void bn_finalize_tiles_kernel(const float* __restrict__ part, int tiles, long rpt, int C, long R,
-                                   const float* __restrict__ gamma, const float* __restrict__ beta,
-                                   float* __restrict__ running_mean, float* __restrict__ running_var, float momentum, float eps,
-                                   float* __restrict__ save_mean, float* __restrict__ save_rstd,
-                                   float* __restrict__ scale, float* __restrict__ shift) {
+__global__ __launch_bounds__(FT_C * FT_L) void bn_finalize_tiles_kernel(const float* __restrict__ part, int tiles, long rpt, int C, long R, const BnFin f) {
     // 16 channels x 64 tile lanes per block (C / 16 blocks): with 64 channels per block a 64-channel layer was ONE block walking
     // 1,024 row blocks 16 at a time -- 15 us per call of pure latency, 78 calls per step
     __shared__ double s1[FT_L][FT_C], s2[FT_L][FT_C];
@@ -182,19 +202,7 @@ __global__ __launch_bounds__(FT_C * FT_L) void bn_finalize_tiles_kernel(const fl
     a = s1[0][tx]; b = s2[0][tx];
     const double n = (double)R;
     const double mean = a / n;
-    double var = b / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    save_mean[c] = (float)mean;
-    save_rstd[c] = rstd;
-    if (running_mean != nullptr) {
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-        const double unb = R > 1 ? var * n / (n - 1.0) : var;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
-    const float sc = gamma[c] * rstd;
-    scale[c] = sc;
-    shift[c] = beta[c] - (float)mean * sc;
+    bn_finish_channel(c, mean, b / n - mean * mean, R, f);
 }
 struct TileStats { const float* part; long tiles, rows; };
 
@@ -208,226 +216,29 @@ __global__ void bn_eval_coeff_kernel(int C, const float* __restrict__ gamma, con
     shift[c] = beta[c] - rm[c] * sc;
 }
 
-// y = act(scale*x + shift (+ res))
+// y = act(scale*x + shift (+ res)).  A streaming pass on the block shape of the reductions: per-channel coefficients live in
+// registers, no index division, 4 independent loads per operand in flight per thread.
+// y16 (bf16 mode, optional, V = 4): the same values rounded to bf16 beside y, same leading dimension -- the shadow the bf16 GEMMs read
+template <int V, bool X16>
 __global__ __launch_bounds__(256) void affine_apply_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, const float* __restrict__ res, int ldr,
-                                                           float* __restrict__ y, int ldy, int C, long total, int relu) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long r = i / C;
-        const int c = (int)(i - r * C);
-        float v = fmaf(x[r * ldx + c], scale[c], shift[c]);
-        if (res != nullptr) v += res[r * ldr + c];
-        if (relu) v = fmaxf(v, 0.f);
-        y[r * ldy + c] = v;
-    }
-}
-
-
-// ---- float4 variants of the column reductions: 16 channel-quads (64 channels) x 16 row-lanes per block, 4 rows in
-// flight per thread.  The scalar forms above moved 1.1-1.6 TB/s (one 4-byte load in flight per thread).
-#define V4_TX 16
-#define V4_TY 16
-// rows a block of the float4 kernels walks: rows_per_chunk > 0: its own contiguous chunk [blockIdx.y * rpc, ...); < 0: the chunks taken
-// from the END of the tensor (bn_second_pass_reverse); == 0: INTERLEAVED -- block y takes the 16-row groups y, y + gridDim.y, ... so the
-// whole grid reads one moving window of the tensor instead of gridDim.y separate streams (bn_interleave)
-__device__ __forceinline__ void v4_rows(long rows_per_chunk, long R, int ty, long& rs, long& re, long& rstep) {
-    if (rows_per_chunk == 0) { rs = (long)blockIdx.y * V4_TY + ty; re = R; rstep = (long)gridDim.y * V4_TY; return; }
-    const long rpc = rows_per_chunk < 0 ? -rows_per_chunk : rows_per_chunk;
-    const long r0 = (rows_per_chunk < 0 ? (long)(gridDim.y - 1 - blockIdx.y) : (long)blockIdx.y) * rpc;
-    rs = r0 + ty; re = min(R, r0 + rpc); rstep = V4_TY;
-}
-__device__ __forceinline__ void v4_block_reduce(float4 a, float4 b, float4 (&sa)[V4_TY][V4_TX], float4 (&sb)[V4_TY][V4_TX],
-                                                float* __restrict__ part, int C, int c0, bool two, bool wt = false) {
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
-    sa[ty][tx] = a; sb[ty][tx] = b;
-    __syncthreads();
-    if (ty == 0 && c0 < C) {
-        float4 x = sa[0][tx], y = sb[0][tx];
-        for (int j = 1; j < V4_TY; ++j) {
-            float4 u = sa[j][tx], v = sb[j][tx];
-            x.x += u.x; x.y += u.y; x.z += u.z; x.w += u.w;
-            y.x += v.x; y.y += v.y; y.z += v.z; y.w += v.w;
-        }
-        float* o = part + ((long)blockIdx.y * C + c0) * 2;
-        const float v[8] = {x.x, two ? y.x : 0.f, x.y, two ? y.y : 0.f, x.z, two ? y.z : 0.f, x.w, two ? y.w : 0.f};
-        if (wt) {                                            // consumed by another block of this launch: write-through stores
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pdf_store_wt(o + e, v[e]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = v[e];
-        }
-    }
-}
-
-
-// bf16 storage mode: the BatchNorm input x (a conv output nobody else reads) may come as bf16 (X16): 4 channels = one 8-byte load
-template <bool X16>
-__device__ __forceinline__ float4 ld_x4(const float* __restrict__ x, long idx) {
-    if constexpr (X16) {
-        const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(x) + idx);
-        return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-    } else {
-        return *reinterpret_cast<const float4*>(x + idx);
-    }
-}
-
-template <bool X16 = false>
-__global__ __launch_bounds__(256) void bn_partial_v4_kernel(const float* __restrict__ x, int ldx, int C, long R, long rows_per_chunk,
-                                                            float* __restrict__ part, const BnFin fin) {
-    __shared__ float4 sa[V4_TY][V4_TX], sb[V4_TY][V4_TX];
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
-    const int c0 = blockIdx.x * BN_CT + tx * 4;
-    long rs, re, rstep;
-    v4_rows(rows_per_chunk, R, ty, rs, re, rstep);
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-    if (c0 < C) {
-        const float4 sh = ld_x4<X16>(x, c0);
-        if (X16 && blockIdx.y == 0 && ty == 0) *reinterpret_cast<float4*>(fin.shift0 + c0) = sh;      // (the finaliser's `x[c]`: row 0 as floats)
-#pragma unroll 4
-        for (long r = rs; r < re; r += rstep) {
-            float4 v = ld_x4<X16>(x, r * ldx + c0);
-            v.x -= sh.x; v.y -= sh.y; v.z -= sh.z; v.w -= sh.w;
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-            b.x += v.x * v.x; b.y += v.y * v.y; b.z += v.z * v.z; b.w += v.w * v.w;
-        }
-    }
-    v4_block_reduce(a, b, sa, sb, part, C, c0, true, fin.counters != nullptr);
-    if (fin.counters != nullptr) {
-        __shared__ double red[512];
-        __shared__ int flag;
-        if (pdf_last_block_arrives(fin.counters + blockIdx.x, gridDim.y, &flag, false)) bn_finalize_tile(part, gridDim.y, X16 ? fin.shift0 : x, C, R, fin, blockIdx.x, red);
-    }
-}
-
-// relu == 2: no residual went into the ReLU, so its mask is recomputed from x as fmaf(x, scale, shift) > 0 -- the exact
-// expression of the forward -- and y is not read at all
-template <bool X16 = false>
-__global__ __launch_bounds__(256) void bn_bwd_partial_v4_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int relu,
-                                                                const float* __restrict__ x, int ldx, const float* __restrict__ mean,
-                                                                const float* __restrict__ rstd, const float* __restrict__ scale,
-                                                                const float* __restrict__ shift, int C, long R, long rows_per_chunk,
-                                                                float* __restrict__ part, const BnBwdFin fin) {
-    __shared__ float4 sa[V4_TY][V4_TX], sb[V4_TY][V4_TX];
-    const long RT = R;
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
-    const int c0 = blockIdx.x * BN_CT + tx * 4;
-    long row_s, row_e, row_step;
-    v4_rows(rows_per_chunk, R, ty, row_s, row_e, row_step);
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-    if (c0 < C) {
-        const float4 m = *reinterpret_cast<const float4*>(mean + c0), rs = *reinterpret_cast<const float4*>(rstd + c0);
-        float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
-        if (relu == 2) { sc = *reinterpret_cast<const float4*>(scale + c0); sh = *reinterpret_cast<const float4*>(shift + c0); }
-#pragma unroll 4
-        for (long r = row_s; r < row_e; r += row_step) {
-            float4 g = *reinterpret_cast<const float4*>(dy + r * lddy + c0);
-            const float4 xv = ld_x4<X16>(x, r * ldx + c0);
-            if (relu) {
-                const float4 yv = relu == 2 ? make_float4(fmaf(xv.x, sc.x, sh.x), fmaf(xv.y, sc.y, sh.y), fmaf(xv.z, sc.z, sh.z), fmaf(xv.w, sc.w, sh.w))
-                                            : *reinterpret_cast<const float4*>(y + r * ldy + c0);
-                if (!(yv.x > 0.f)) g.x = 0.f;
-                if (!(yv.y > 0.f)) g.y = 0.f;
-                if (!(yv.z > 0.f)) g.z = 0.f;
-                if (!(yv.w > 0.f)) g.w = 0.f;
-            }
-            a.x += g.x; a.y += g.y; a.z += g.z; a.w += g.w;
-            b.x += g.x * (xv.x - m.x) * rs.x; b.y += g.y * (xv.y - m.y) * rs.y;
-            b.z += g.z * (xv.z - m.z) * rs.z; b.w += g.w * (xv.w - m.w) * rs.w;
-        }
-    }
-    v4_block_reduce(a, b, sa, sb, part, C, c0, true, fin.counters != nullptr);
-    if (fin.counters != nullptr) {
-        __shared__ double red[512];
-        __shared__ int flag;
-        if (pdf_last_block_arrives(fin.counters + blockIdx.x, gridDim.y, &flag, false)) bn_bwd_finalize_tile(part, gridDim.y, C, RT, fin, blockIdx.x, red);
-    }
-}
-
-// (colsum kernels: blockIdx.z == 1 is group 1 of a paired call -- rows [R, 2R), partials after group 0's)
-__global__ __launch_bounds__(256) void colsum_partial_v4_kernel(const float* __restrict__ g, int ldg, int C, long R, long rows_per_chunk,
-                                                                float* __restrict__ part) {
-    __shared__ float4 sa[V4_TY][V4_TX], sb[V4_TY][V4_TX];
-    if (blockIdx.z) { g += R * ldg; part += (long)gridDim.y * C * 2; }
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
-    const int c0 = blockIdx.x * BN_CT + tx * 4;
+                                                           float* __restrict__ y, int ldy, int C, long R, long rows_per_chunk, int relu,
+                                                           unsigned short* __restrict__ y16) {
+    const int tx = threadIdx.x & (BN_TX(V) - 1), ty = threadIdx.x / BN_TX(V);
+    const int c0 = blockIdx.x * BN_CT + tx * V;
+    if (c0 >= C) return;
     const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c0 < C) {
+    const vf<V> sc = vld<V>(scale + c0), sh = vld<V>(shift + c0);
 #pragma unroll 4
-        for (long r = r0 + ty; r < r1; r += V4_TY) {
-            const float4 v = *reinterpret_cast<const float4*>(g + r * ldg + c0);
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-        }
-    }
-    v4_block_reduce(a, a, sa, sb, part, C, c0, false);
-}
-
-// float4 streaming passes on the same (16 channel-quads x 16 row-lanes) block shape: per-channel coefficients live in
-// registers, no index division, 4 independent 16-byte loads per operand in flight per thread.
-template <bool X16 = false>
-__global__ __launch_bounds__(256) void affine_apply_v4_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ scale,
-                                                              const float* __restrict__ shift, const float* __restrict__ res, int ldr,
-                                                              float* __restrict__ y, int ldy, int C, long R, long rows_per_chunk, int relu,
-                                                              unsigned short* __restrict__ y16 = nullptr) {
-    // y16 (bf16 mode, optional): the same values rounded to bf16 beside y, same leading dimension -- the shadow the bf16 GEMMs read
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
-    const int c0 = blockIdx.x * BN_CT + tx * 4;
-    if (c0 >= C) return;
-    long row_s, row_e, row_step;
-    v4_rows(rows_per_chunk, R, ty, row_s, row_e, row_step);
-    const float4 sc = *reinterpret_cast<const float4*>(scale + c0), sh = *reinterpret_cast<const float4*>(shift + c0);
-#pragma unroll 4
-    for (long r = row_s; r < row_e; r += row_step) {
-        const float4 xv = ld_x4<X16>(x, r * ldx + c0);
-        float4 v = make_float4(fmaf(xv.x, sc.x, sh.x), fmaf(xv.y, sc.y, sh.y), fmaf(xv.z, sc.z, sh.z), fmaf(xv.w, sc.w, sh.w));
-        if (res != nullptr) {
-            const float4 rv = *reinterpret_cast<const float4*>(res + r * ldr + c0);
-            v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-        }
-        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        *reinterpret_cast<float4*>(y + r * ldy + c0) = v;
-        if (y16 != nullptr) *reinterpret_cast<uint2*>(y16 + r * ldy + c0) = uint2{pdf_pk_bf16(v.x, v.y), pdf_pk_bf16(v.z, v.w)};
-    }
-}
-
-template <bool X16 = false>
-__global__ __launch_bounds__(256) void bn_bwd_apply_v4_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int relu,
-                                                              const float* __restrict__ x, int ldx, const float* __restrict__ mean,
-                                                              const float* __restrict__ rstd, const float* __restrict__ coef,
-                                                              const float* __restrict__ scale, const float* __restrict__ shift, int C, long R,
-                                                              long rows_per_chunk, float* __restrict__ dx, int lddx, float* __restrict__ dres, int lddr,
-                                                              unsigned short* __restrict__ dx16 = nullptr) {
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
-    const int c0 = blockIdx.x * BN_CT + tx * 4;
-    if (c0 >= C) return;
-    long row_s, row_e, row_step;
-    v4_rows(rows_per_chunk, R, ty, row_s, row_e, row_step);
-    const float4 m = *reinterpret_cast<const float4*>(mean + c0), rs = *reinterpret_cast<const float4*>(rstd + c0);
-    const float4 ka = *reinterpret_cast<const float4*>(coef + c0), k1 = *reinterpret_cast<const float4*>(coef + C + c0),
-                 k2 = *reinterpret_cast<const float4*>(coef + 2 * C + c0);
-    float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
-    if (relu == 2) { sc = *reinterpret_cast<const float4*>(scale + c0); sh = *reinterpret_cast<const float4*>(shift + c0); }
-#pragma unroll 4
-    for (long r = row_s; r < row_e; r += row_step) {
-        float4 g = *reinterpret_cast<const float4*>(dy + r * lddy + c0);
-        const float4 xv = ld_x4<X16>(x, r * ldx + c0);
+    for (long r = r0 + ty; r < r1; r += BN_TY(V)) {
+        vf<V> v = vfma<V>(ld_x<V, X16>(x, r * ldx + c0), sc, sh);
+        if (res != nullptr) v += vld<V>(res + r * ldr + c0);
         if (relu) {
-            const float4 yv = relu == 2 ? make_float4(fmaf(xv.x, sc.x, sh.x), fmaf(xv.y, sc.y, sh.y), fmaf(xv.z, sc.z, sh.z), fmaf(xv.w, sc.w, sh.w))
-                                        : *reinterpret_cast<const float4*>(y + r * ldy + c0);
-            if (!(yv.x > 0.f)) g.x = 0.f;
-            if (!(yv.y > 0.f)) g.y = 0.f;
-            if (!(yv.z > 0.f)) g.z = 0.f;
-            if (!(yv.w > 0.f)) g.w = 0.f;
+#pragma unroll
+            for (int i = 0; i < V; ++i) v[i] = fmaxf(v[i], 0.f);
         }
-        if (dres != nullptr) *reinterpret_cast<float4*>(dres + r * lddr + c0) = g;
-        float4 o;
-        o.x = ka.x * (g.x - k1.x - (xv.x - m.x) * rs.x * k2.x);
-        o.y = ka.y * (g.y - k1.y - (xv.y - m.y) * rs.y * k2.y);
-        o.z = ka.z * (g.z - k1.z - (xv.z - m.z) * rs.z * k2.z);
-        o.w = ka.w * (g.w - k1.w - (xv.w - m.w) * rs.w * k2.w);
-        if (dx != nullptr) *reinterpret_cast<float4*>(dx + r * lddx + c0) = o;
-        if (dx16 != nullptr) *reinterpret_cast<uint2*>(dx16 + r * lddx + c0) = uint2{pdf_pk_bf16(o.x, o.y), pdf_pk_bf16(o.z, o.w)};
+        vst<V>(y + r * ldy + c0, v);
+        if constexpr (V == 4) if (y16 != nullptr) vst_bf16(y16 + r * ldy + c0, v);
     }
 }
 
@@ -438,20 +249,7 @@ static long apply_rows_per_chunk(int C, long R) {
     if (want < 1) want = 1;
     long rpc = (R + want - 1) / want;
     if (rpc < 64) rpc = 64;
-    return (rpc + V4_TY - 1) / V4_TY * V4_TY;
-}
-
-// The second pass of a two-pass operator (BatchNorm forward: statistics, then apply; backward: sums, then apply) re-reads what the first
-// pass has just streamed.  The 256 MiB Infinity Cache is memory-side and keeps what was touched most recently (MI355X_MICROARCH.md
-// "Infinity Cache"): walking the tensor in the SAME order evicts a line just before it is wanted again once the operands exceed the
-// cache; walking it BACKWARDS meets the most recently read rows first.  sign(rows_per_chunk) carries the order into the kernels.
-static int bn_interleave() {                                  // 1: partial passes, 2: apply passes, 3: both (PDF_BN_INTERLEAVE)
-    static const int v = getenv("PDF_BN_INTERLEAVE") ? atoi(getenv("PDF_BN_INTERLEAVE")) : 0;
-    return v;
-}
-static int bn_second_pass_reverse() {
-    static const int v = getenv("PDF_BN_REVERSE") ? atoi(getenv("PDF_BN_REVERSE")) : 0;
-    return v;
+    return (rpc + BN_TY(4) - 1) / BN_TY(4) * BN_TY(4);
 }
 static bool v4_ok(int C, std::initializer_list<int> lds, std::initializer_list<const void*> ptrs) {
     if (C % 4) return false;
@@ -459,19 +257,20 @@ static bool v4_ok(int C, std::initializer_list<int> lds, std::initializer_list<c
     for (const void* p : ptrs) if (p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15)) return false;
     return true;
 }
+// kern<V, X16> in the instantiation the operands allow: <4, true> (bf16 input; the caller checked v4_ok), <4, false>, <1, false>
+#define BN_LAUNCH(kern, vec, x16, grid, s, ...)                                                           \
+    do {                                                                                                  \
+        if (x16) hipLaunchKernelGGL((kern<4, true>), grid, dim3(256), 0, s, __VA_ARGS__);                 \
+        else if (vec) hipLaunchKernelGGL((kern<4, false>), grid, dim3(256), 0, s, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((kern<1, false>), grid, dim3(256), 0, s, __VA_ARGS__);                    \
+    } while (0)
 
 static void launch_affine_apply(const float* x, int ldx, const float* scale, const float* shift, const float* res, int ldr,
                                 float* y, int ldy, int C, long R, int relu, hipStream_t s, void* y16 = nullptr, const void* x16 = nullptr) {
-    if (x16 != nullptr) {                                    // (the caller checked v4_ok)
-        const long rpc = apply_rows_per_chunk(C, R);
-        hipLaunchKernelGGL((affine_apply_v4_kernel<true>), dim3(cdiv(C, BN_CT), (unsigned)((R + rpc - 1) / rpc)), dim3(256), 0, s,
-                           reinterpret_cast<const float*>(x16), ldx, scale, shift, res, ldr, y, ldy, C, R, (bn_interleave() & 2) ? 0 : bn_second_pass_reverse() ? -rpc : rpc, relu, reinterpret_cast<unsigned short*>(y16));
-    } else if (v4_ok(C, {ldx, ldy, res ? ldr : 0}, {x, y, res, scale, shift})) {
-        const long rpc = apply_rows_per_chunk(C, R);
-        hipLaunchKernelGGL((affine_apply_v4_kernel<false>), dim3(cdiv(C, BN_CT), (unsigned)((R + rpc - 1) / rpc)), dim3(256), 0, s,
-                           x, ldx, scale, shift, res, ldr, y, ldy, C, R, (bn_interleave() & 2) ? 0 : bn_second_pass_reverse() ? -rpc : rpc, relu, reinterpret_cast<unsigned short*>(y16));
-    } else
-        hipLaunchKernelGGL(affine_apply_kernel, dim3(grid_for(R * C)), dim3(256), 0, s, x, ldx, scale, shift, res, ldr, y, ldy, C, R * C, relu);
+    const bool vec = x16 != nullptr || v4_ok(C, {ldx, ldy, res ? ldr : 0}, {x, y, res, scale, shift});      // (x16: the caller checked v4_ok)
+    const long rpc = apply_rows_per_chunk(C, R);
+    BN_LAUNCH(affine_apply_kernel, vec, x16 != nullptr, dim3(cdiv(C, BN_CT), (unsigned)((R + rpc - 1) / rpc)), s,
+              x16 != nullptr ? reinterpret_cast<const float*>(x16) : x, ldx, scale, shift, res, ldr, y, ldy, C, R, rpc, relu, reinterpret_cast<unsigned short*>(y16));
 }
 
 // Training forward.  ws: >= pdf_bn_workspace_floats(C, R) floats.  scale/shift [C] are outputs the
@@ -490,9 +289,16 @@ static long bn_chunks(int C, long R) {
     if (want < 1) want = 1;
     return want;
 }
+// the row chunks of a reduction pass over R rows: `chunks` blocks of `rpc` rows (the last one may be short), none empty
+struct BnSplit { long rpc, chunks; };
+static BnSplit bn_split(int C, long R) {
+    const long want = bn_chunks(C, R);
+    const long rpc = (R + want - 1) / want;
+    return {rpc, (R + rpc - 1) / rpc};
+}
 PDF_API long pdf_bn_workspace_floats(int C, long R) {
     long chunks = bn_chunks(C, R);
-    return chunks * C * 2 + C;                              // (+ C: row 0 of a bf16 input as floats, BnFin::shift0)
+    return chunks * C * 2 + C;                              // (+ C: row 0 of a bf16 input as floats, the `shift0` of bn_partial_kernel)
 }
 // bf16 storage mode (PdfCallOpts::bn_x_bf16): pdf_bn_train_fwd / pdf_bn_train_bwd read their input x from a bf16 tensor (same shape and
 // leading dimension in elements) instead of the fp32 pointer they are given
@@ -507,29 +313,21 @@ static int pdf_bn_train_fwd_impl(const float* x, int ldx, int C, long R, const f
     const void* x16 = co.bn_x_bf16;
     if (R <= 0 || C <= 0) return 0;
     if (x16 != nullptr && !v4_ok(C, {ldx, ldy, res ? ldr : 0}, {x16, y, res, scale, shift})) return PDF_E_BADARG;
-    long chunks = bn_chunks(C, R);
-    long rpc = (R + chunks - 1) / chunks;
-    chunks = (R + rpc - 1) / rpc;
-    BnFin fin = {gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_rstd, scale, shift, nullptr, ws + bn_chunks(C, R) * C * 2};
-    if (ts.part != nullptr) {                                // statistics came out of the producing GEMM's epilogue: no pass over x
+    const BnFin fin = {gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_rstd, scale, shift};
+    const bool from_tiles = ts.part != nullptr;              // statistics came out of the producing GEMM's epilogue: no pass over x
+    if (from_tiles) {
         if (ts.tiles * ts.rows < R || (ts.tiles - 1) * ts.rows >= R) return PDF_E_BADARG;
-        hipLaunchKernelGGL(bn_finalize_tiles_kernel, dim3(cdiv(C, FT_C)), dim3(FT_C * FT_L), 0, s, ts.part, (int)ts.tiles, ts.rows, C, R, gamma, beta,
-                           running_mean, running_var, momentum, eps, save_mean, save_rstd, scale, shift);
-        fin.counters = reinterpret_cast<int*>(1);            // (marks "finalised" for the branch below)
-    } else if (x16 != nullptr) {
-        fin.counters = bn_inlaunch(C, R) ? pdf_ticket_counters(cdiv(C, BN_CT)) : nullptr;
-        hipLaunchKernelGGL((bn_partial_v4_kernel<true>), dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, reinterpret_cast<const float*>(x16), ldx, C, R, (bn_interleave() & 1) ? 0 : rpc, ws, fin);
-    } else if (v4_ok(C, {ldx}, {x})) {
-        fin.counters = bn_inlaunch(C, R) ? pdf_ticket_counters(cdiv(C, BN_CT)) : nullptr;          // finalize in the last block of each channel tile
-        hipLaunchKernelGGL((bn_partial_v4_kernel<false>), dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, x, ldx, C, R, (bn_interleave() & 1) ? 0 : rpc, ws, fin);
-    } else
-        hipLaunchKernelGGL(bn_partial_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, x, ldx, C, R, rpc, ws);
-    PDF_LAUNCH_CHECK();
-    if (fin.counters == nullptr) {
-        hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, x16 != nullptr ? fin.shift0 : x, C, R, gamma, beta,
-                           running_mean, running_var, momentum, eps, save_mean, save_rstd, scale, shift);
+        hipLaunchKernelGGL(bn_finalize_tiles_kernel, dim3(cdiv(C, FT_C)), dim3(FT_C * FT_L), 0, s, ts.part, (int)ts.tiles, ts.rows, C, R, fin);
+    } else {
+        const BnSplit sp = bn_split(C, R);
+        float* shift0 = ws + bn_chunks(C, R) * C * 2;        // X16: row 0 of x as floats, written by the partial kernel
+        const bool vec = x16 != nullptr || v4_ok(C, {ldx}, {x});
+        BN_LAUNCH(bn_partial_kernel, vec, x16 != nullptr, dim3(cdiv(C, BN_CT), (unsigned)sp.chunks), s,
+                  x16 != nullptr ? reinterpret_cast<const float*>(x16) : x, ldx, C, R, sp.rpc, ws, shift0);
         PDF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)sp.chunks, x16 != nullptr ? shift0 : x, C, R, fin);
     }
+    PDF_LAUNCH_CHECK();
     if (y == nullptr) return res == nullptr && y16 == nullptr ? 0 : PDF_E_BADARG;      // statistics and coefficients only: the consumer applies them (pdf_set_input_affine_relu)
     if (x16 == nullptr && y16 != nullptr && !v4_ok(C, {ldx, ldy, res ? ldr : 0}, {x, y, res, scale, shift, y16})) return PDF_E_BADARG;
     launch_affine_apply(x, ldx, scale, shift, res, ldr, y, ldy, C, R, relu, s, y16, x16);
@@ -565,31 +363,30 @@ PDF_API int pdf_bn_eval_fwd(const float* x, int ldx, int C, long R, const float*
 }
 
 // backward partials: sum(g), sum(g * xhat) with g = dy * (y > 0 if relu)
+template <int V, bool X16>
 __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int relu,
                                                              const float* __restrict__ x, int ldx, const float* __restrict__ mean,
                                                              const float* __restrict__ rstd, const float* __restrict__ scale,
                                                              const float* __restrict__ shift, int C, long R, long rows_per_chunk,
                                                              float* __restrict__ part) {
-    __shared__ float s1[4][BN_CT], s2[4][BN_CT];
-    const int tx = threadIdx.x & (BN_CT - 1), ty = threadIdx.x / BN_CT;
-    const int c = blockIdx.x * BN_CT + tx;
-    const long r0 = blockIdx.y * rows_per_chunk;
-    const long r1 = min(R, r0 + rows_per_chunk);
-    float a = 0.f, b = 0.f;
-    if (c < C) {
-        const float m = mean[c], rs = rstd[c];
-        for (long r = r0 + ty; r < r1; r += 4) {
-            float g = dy[r * lddy + c];
-            if (relu && !((relu == 2 ? fmaf(x[r * ldx + c], scale[c], shift[c]) : y[r * ldy + c]) > 0.f)) g = 0.f;
-            a += g; b += g * (x[r * ldx + c] - m) * rs;
+    __shared__ vf<V> sa[BN_TY(V)][BN_TX(V)], sb[BN_TY(V)][BN_TX(V)];
+    const int tx = threadIdx.x & (BN_TX(V) - 1), ty = threadIdx.x / BN_TX(V);
+    const int c0 = blockIdx.x * BN_CT + tx * V;
+    const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
+    vf<V> a = {}, b = {};
+    if (c0 < C) {
+        const vf<V> m = vld<V>(mean + c0), rs = vld<V>(rstd + c0);
+        vf<V> sc = {}, sh = {};
+        if (relu == 2) { sc = vld<V>(scale + c0); sh = vld<V>(shift + c0); }
+#pragma unroll 4
+        for (long r = r0 + ty; r < r1; r += BN_TY(V)) {
+            vf<V> g = vld<V>(dy + r * lddy + c0);
+            const vf<V> xv = ld_x<V, X16>(x, r * ldx + c0);
+            g = bn_masked_grad<V>(g, relu, y + r * ldy + c0, xv, sc, sh);
+            a += g; b = bn_acc<V>(b, g * (xv - m), rs);
         }
     }
-    s1[ty][tx] = a; s2[ty][tx] = b;
-    __syncthreads();
-    if (ty == 0 && c < C) {
-        part[((long)blockIdx.y * C + c) * 2 + 0] = s1[0][tx] + s1[1][tx] + s1[2][tx] + s1[3][tx];
-        part[((long)blockIdx.y * C + c) * 2 + 1] = s2[0][tx] + s2[1][tx] + s2[2][tx] + s2[3][tx];
-    }
+    bn_block_reduce<V>(a, b, sa, sb, part, C, c0, true);
 }
 
 __global__ __launch_bounds__(FIN_TX * FIN_TY) void bn_bwd_finalize_kernel(const float* __restrict__ part, int chunks, int C, long R, const float* __restrict__ gamma,
@@ -607,20 +404,31 @@ __global__ __launch_bounds__(FIN_TX * FIN_TY) void bn_bwd_finalize_kernel(const 
     coef[2 * C + c] = (float)(b / (double)R);
 }
 
-// dx = a * (g - c1 - xhat * c2);  dres = g (optional)
+// dx = a * (g - c1 - xhat * c2);  dres = g (optional);  dx16 (optional, V = 4): dx rounded to bf16
+template <int V, bool X16>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int relu,
                                                            const float* __restrict__ x, int ldx, const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, const float* __restrict__ coef,
-                                                           const float* __restrict__ scale, const float* __restrict__ shift, int C, long total,
-                                                           float* __restrict__ dx, int lddx, float* __restrict__ dres, int lddr) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long r = i / C;
-        const int c = (int)(i - r * C);
-        float g = dy[r * lddy + c];
-        if (relu && !((relu == 2 ? fmaf(x[r * ldx + c], scale[c], shift[c]) : y[r * ldy + c]) > 0.f)) g = 0.f;
-        if (dres != nullptr) dres[r * lddr + c] = g;
-        const float xh = (x[r * ldx + c] - mean[c]) * rstd[c];
-        dx[r * lddx + c] = coef[c] * (g - coef[C + c] - xh * coef[2 * C + c]);
+                                                           const float* __restrict__ scale, const float* __restrict__ shift, int C, long R,
+                                                           long rows_per_chunk, float* __restrict__ dx, int lddx, float* __restrict__ dres, int lddr,
+                                                           unsigned short* __restrict__ dx16) {
+    const int tx = threadIdx.x & (BN_TX(V) - 1), ty = threadIdx.x / BN_TX(V);
+    const int c0 = blockIdx.x * BN_CT + tx * V;
+    if (c0 >= C) return;
+    const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
+    const vf<V> m = vld<V>(mean + c0), rs = vld<V>(rstd + c0);
+    const vf<V> ka = vld<V>(coef + c0), k1 = vld<V>(coef + C + c0), k2 = vld<V>(coef + 2 * C + c0);
+    vf<V> sc = {}, sh = {};
+    if (relu == 2) { sc = vld<V>(scale + c0); sh = vld<V>(shift + c0); }
+#pragma unroll 4
+    for (long r = r0 + ty; r < r1; r += BN_TY(V)) {
+        vf<V> g = vld<V>(dy + r * lddy + c0);
+        const vf<V> xv = ld_x<V, X16>(x, r * ldx + c0);
+        g = bn_masked_grad<V>(g, relu, y + r * ldy + c0, xv, sc, sh);
+        if (dres != nullptr) vst<V>(dres + r * lddr + c0, g);
+        const vf<V> o = ka * (g - k1 - (xv - m) * rs * k2);
+        if (dx != nullptr) vst<V>(dx + r * lddx + c0, o);
+        if constexpr (V == 4) if (dx16 != nullptr) vst_bf16(dx16 + r * lddx + c0, o);
     }
 }
 
@@ -638,44 +446,21 @@ static int pdf_bn_train_bwd_impl(const float* dy, int lddy, const float* y, int 
     if (R <= 0 || C <= 0) return 0;
     if ((relu == 1 && y == nullptr) || (relu == 2 && (scale == nullptr || shift == nullptr || dres != nullptr))) return PDF_E_BADARG;
     if (dx == nullptr && dx16 == nullptr) return PDF_E_BADARG;
-    long chunks = bn_chunks(C, R);
-    long rpc = (R + chunks - 1) / chunks;
-    chunks = (R + rpc - 1) / rpc;
+    const BnSplit sp = bn_split(C, R);
     float* coef = ws + pdf_bn_workspace_floats(C, R);
     const float* xin = x16 != nullptr ? reinterpret_cast<const float*>(x16) : x;
     const bool vec = v4_ok(C, {lddy, ldx, lddx, relu == 1 ? ldy : 0, dres ? lddr : 0},
                            {dy, xin, dx, dres, relu == 1 ? y : nullptr, save_mean, save_rstd, coef, relu == 2 ? scale : nullptr, relu == 2 ? shift : nullptr});
     if ((x16 != nullptr || dx == nullptr) && !vec) return PDF_E_BADARG;
-    BnBwdFin fin = {gamma, save_rstd, dgamma, dbeta, accumulate, coef, nullptr};
-    if (vec) {
-        fin.counters = bn_inlaunch(C, R) ? pdf_ticket_counters(cdiv(C, BN_CT)) : nullptr;
-        if (x16 != nullptr)
-            hipLaunchKernelGGL((bn_bwd_partial_v4_kernel<true>), dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dy, lddy, y, ldy, relu, xin, ldx,
-                               save_mean, save_rstd, scale, shift, C, R, (bn_interleave() & 1) ? 0 : rpc, ws, fin);
-        else
-            hipLaunchKernelGGL((bn_bwd_partial_v4_kernel<false>), dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dy, lddy, y, ldy, relu, x, ldx,
-                               save_mean, save_rstd, scale, shift, C, R, (bn_interleave() & 1) ? 0 : rpc, ws, fin);
-    } else
-        hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dy, lddy, y, ldy, relu, x, ldx,
-                           save_mean, save_rstd, scale, shift, C, R, rpc, ws);
+    BN_LAUNCH(bn_bwd_partial_kernel, vec, x16 != nullptr, dim3(cdiv(C, BN_CT), (unsigned)sp.chunks), s, dy, lddy, y, ldy, relu, xin, ldx,
+              save_mean, save_rstd, scale, shift, C, R, sp.rpc, ws);
     PDF_LAUNCH_CHECK();
-    if (fin.counters == nullptr) {
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, C, R, gamma, save_rstd, dgamma, dbeta, accumulate, coef);
-        PDF_LAUNCH_CHECK();
-    }
-    if (vec) {
-        const long arpc = apply_rows_per_chunk(C, R);
-        const dim3 grid(cdiv(C, BN_CT), (unsigned)((R + arpc - 1) / arpc));
-        if (x16 != nullptr)
-            hipLaunchKernelGGL((bn_bwd_apply_v4_kernel<true>), grid, dim3(256), 0, s, dy, lddy, y, ldy, relu,
-                               xin, ldx, save_mean, save_rstd, coef, scale, shift, C, R, (bn_interleave() & 2) ? 0 : bn_second_pass_reverse() ? -arpc : arpc, dx, lddx, dres, lddr, reinterpret_cast<unsigned short*>(dx16));
-        else
-            hipLaunchKernelGGL((bn_bwd_apply_v4_kernel<false>), grid, dim3(256), 0, s, dy, lddy, y, ldy, relu,
-                               x, ldx, save_mean, save_rstd, coef, scale, shift, C, R, (bn_interleave() & 2) ? 0 : bn_second_pass_reverse() ? -arpc : arpc, dx, lddx, dres, lddr, reinterpret_cast<unsigned short*>(dx16));
-    } else if (dx16 != nullptr) return PDF_E_BADARG;
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(R * C)), dim3(256), 0, s, dy, lddy, y, ldy, relu, x, ldx, save_mean, save_rstd, coef,
-                           scale, shift, C, R * C, dx, lddx, dres, lddr);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)sp.chunks, C, R, gamma, save_rstd, dgamma, dbeta, accumulate, coef);
+    PDF_LAUNCH_CHECK();
+    if (!vec && dx16 != nullptr) return PDF_E_BADARG;
+    const long arpc = apply_rows_per_chunk(C, R);
+    BN_LAUNCH(bn_bwd_apply_kernel, vec, x16 != nullptr, dim3(cdiv(C, BN_CT), (unsigned)((R + arpc - 1) / arpc)), s, dy, lddy, y, ldy, relu,
+              xin, ldx, save_mean, save_rstd, coef, scale, shift, C, R, arpc, dx, lddx, dres, lddr, reinterpret_cast<unsigned short*>(dx16));
     PDF_LAUNCH_CHECK();
     return 0;
 }
@@ -702,89 +487,36 @@ PDF_API int pdf_bn_train_bwd(const float* dy, int lddy, const float* y, int ldy,
 // it leaves in `part` are finished by bn_eval_bwd_finalize_kernel.  xhat comes from the running statistics, never from
 // (y - beta) / gamma: a channel with gamma == 0 still has a dgamma.  SUMS == false (neither parameter wants a gradient): purely
 // element-wise -- no partials, no LDS, no second launch, and x is read only to recompute the mask (relu == 2).
-template <bool SUMS>
-__global__ __launch_bounds__(256) void bn_eval_bwd_v4_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int relu,
-                                                             const float* __restrict__ x, int ldx, const float* __restrict__ rmean,
-                                                             const float* __restrict__ rvar, float eps, const float* __restrict__ scale,
-                                                             const float* __restrict__ shift, int C, long R, long rows_per_chunk,
-                                                             float* __restrict__ dx, int lddx, float* __restrict__ dres, int lddr,
-                                                             float* __restrict__ part) {
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
-    const int c0 = blockIdx.x * BN_CT + tx * 4;
-    long row_s, row_e, row_step;
-    v4_rows(rows_per_chunk, R, ty, row_s, row_e, row_step);
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-    if (c0 < C) {
-        float4 m = a, rs = a, sc = a, sh = a;
-        if (SUMS) {
-            m = *reinterpret_cast<const float4*>(rmean + c0);
-            const float4 v = *reinterpret_cast<const float4*>(rvar + c0);
-            rs = make_float4(1.f / sqrtf(v.x + eps), 1.f / sqrtf(v.y + eps), 1.f / sqrtf(v.z + eps), 1.f / sqrtf(v.w + eps));
-        }
-        if (dx != nullptr || relu == 2) sc = *reinterpret_cast<const float4*>(scale + c0);
-        if (relu == 2) sh = *reinterpret_cast<const float4*>(shift + c0);
-        const bool need_x = SUMS || relu == 2;
-#pragma unroll 4
-        for (long r = row_s; r < row_e; r += row_step) {
-            float4 g = *reinterpret_cast<const float4*>(dy + r * lddy + c0);
-            float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (need_x) xv = *reinterpret_cast<const float4*>(x + r * ldx + c0);
-            if (relu) {
-                const float4 yv = relu == 2 ? make_float4(fmaf(xv.x, sc.x, sh.x), fmaf(xv.y, sc.y, sh.y), fmaf(xv.z, sc.z, sh.z), fmaf(xv.w, sc.w, sh.w))
-                                            : *reinterpret_cast<const float4*>(y + r * ldy + c0);
-                if (!(yv.x > 0.f)) g.x = 0.f;
-                if (!(yv.y > 0.f)) g.y = 0.f;
-                if (!(yv.z > 0.f)) g.z = 0.f;
-                if (!(yv.w > 0.f)) g.w = 0.f;
-            }
-            if (dres != nullptr) *reinterpret_cast<float4*>(dres + r * lddr + c0) = g;
-            if (dx != nullptr) *reinterpret_cast<float4*>(dx + r * lddx + c0) = make_float4(g.x * sc.x, g.y * sc.y, g.z * sc.z, g.w * sc.w);
-            if (SUMS) {
-                a.x += g.x; a.y += g.y; a.z += g.z; a.w += g.w;
-                b.x += g.x * (xv.x - m.x) * rs.x; b.y += g.y * (xv.y - m.y) * rs.y;
-                b.z += g.z * (xv.z - m.z) * rs.z; b.w += g.w * (xv.w - m.w) * rs.w;
-            }
-        }
-    }
-    if constexpr (SUMS) {
-        __shared__ float4 sa[V4_TY][V4_TX], sb[V4_TY][V4_TX];
-        v4_block_reduce(a, b, sa, sb, part, C, c0, true);
-    }
-}
-
-// scalar form (C % 4 != 0, an odd leading dimension, an unaligned pointer): 64 channels x 4 row lanes, the layout of
-// bn_bwd_partial_kernel; part == NULL: no sums
+template <int V, bool SUMS>
 __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy, int relu,
                                                           const float* __restrict__ x, int ldx, const float* __restrict__ rmean,
                                                           const float* __restrict__ rvar, float eps, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, int C, long R, long rows_per_chunk,
                                                           float* __restrict__ dx, int lddx, float* __restrict__ dres, int lddr,
                                                           float* __restrict__ part) {
-    __shared__ float s1[4][BN_CT], s2[4][BN_CT];
-    const int tx = threadIdx.x & (BN_CT - 1), ty = threadIdx.x / BN_CT;
-    const int c = blockIdx.x * BN_CT + tx;
-    const long r0 = blockIdx.y * rows_per_chunk;
-    const long r1 = min(R, r0 + rows_per_chunk);
-    const bool sums = part != nullptr;
-    float a = 0.f, b = 0.f;
-    if (c < C) {
-        const float m = sums ? rmean[c] : 0.f, rs = sums ? 1.f / sqrtf(rvar[c] + eps) : 0.f;
-        const float sc = (dx != nullptr || relu == 2) ? scale[c] : 0.f, sh = relu == 2 ? shift[c] : 0.f;
-        for (long r = r0 + ty; r < r1; r += 4) {
-            float g = dy[r * lddy + c];
-            const float xv = (sums || relu == 2) ? x[r * ldx + c] : 0.f;
-            if (relu && !((relu == 2 ? fmaf(xv, sc, sh) : y[r * ldy + c]) > 0.f)) g = 0.f;
-            if (dres != nullptr) dres[r * lddr + c] = g;
-            if (dx != nullptr) dx[r * lddx + c] = g * sc;
-            a += g; b += g * (xv - m) * rs;
+    const int tx = threadIdx.x & (BN_TX(V) - 1), ty = threadIdx.x / BN_TX(V);
+    const int c0 = blockIdx.x * BN_CT + tx * V;
+    const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
+    vf<V> a = {}, b = {};
+    if (c0 < C) {
+        vf<V> m = {}, rs = {}, sc = {}, sh = {};
+        if (SUMS) { m = vld<V>(rmean + c0); rs = vrsqrt_eps<V>(vld<V>(rvar + c0), eps); }
+        if (dx != nullptr || relu == 2) sc = vld<V>(scale + c0);
+        if (relu == 2) sh = vld<V>(shift + c0);
+        const bool need_x = SUMS || relu == 2;
+#pragma unroll 4
+        for (long r = r0 + ty; r < r1; r += BN_TY(V)) {
+            vf<V> g = vld<V>(dy + r * lddy + c0), xv = {};
+            if (need_x) xv = vld<V>(x + r * ldx + c0);
+            g = bn_masked_grad<V>(g, relu, y + r * ldy + c0, xv, sc, sh);
+            if (dres != nullptr) vst<V>(dres + r * lddr + c0, g);
+            if (dx != nullptr) vst<V>(dx + r * lddx + c0, g * sc);
+            if (SUMS) { a += g; b = bn_acc<V>(b, g * (xv - m), rs); }
         }
     }
-    if (!sums) return;
-    s1[ty][tx] = a; s2[ty][tx] = b;
-    __syncthreads();
-    if (ty == 0 && c < C) {
-        part[((long)blockIdx.y * C + c) * 2 + 0] = s1[0][tx] + s1[1][tx] + s1[2][tx] + s1[3][tx];
-        part[((long)blockIdx.y * C + c) * 2 + 1] = s2[0][tx] + s2[1][tx] + s2[2][tx] + s2[3][tx];
+    if constexpr (SUMS) {
+        __shared__ vf<V> sa[BN_TY(V)][BN_TX(V)], sb[BN_TY(V)][BN_TX(V)];
+        bn_block_reduce<V>(a, b, sa, sb, part, C, c0, true);
     }
 }
 
@@ -813,31 +545,25 @@ PDF_API int pdf_bn_eval_bwd(const float* dy, int lddy, const float* y, int ldy, 
     if ((need_x && x == nullptr) || (dx != nullptr && scale == nullptr)) return PDF_E_BADARG;
     if (sums && (running_mean == nullptr || running_var == nullptr || ws == nullptr)) return PDF_E_BADARG;
     if (!sums && dx == nullptr && dres == nullptr) return 0;
-    long chunks = bn_chunks(C, R);
-    long rpc = (R + chunks - 1) / chunks;
-    chunks = (R + rpc - 1) / rpc;
+    const BnSplit sp = bn_split(C, R);
     const bool use_sc = dx != nullptr || relu == 2;
     const bool vec = v4_ok(C, {lddy, need_x ? ldx : 0, dx ? lddx : 0, relu == 1 ? ldy : 0, dres ? lddr : 0},
                            {dy, need_x ? x : nullptr, dx, dres, relu == 1 ? y : nullptr, sums ? running_mean : nullptr, sums ? running_var : nullptr,
                             use_sc ? scale : nullptr, relu == 2 ? shift : nullptr});
-    if (vec && sums)
-        hipLaunchKernelGGL((bn_eval_bwd_v4_kernel<true>), dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dy, lddy, y, ldy, relu, x, ldx,
-                           running_mean, running_var, eps, scale, shift, C, R, rpc, dx, lddx, dres, lddr, ws);
-    else if (vec) {                                          // element-wise: the finer chunks of the streaming passes
-        const long arpc = apply_rows_per_chunk(C, R);
-        hipLaunchKernelGGL((bn_eval_bwd_v4_kernel<false>), dim3(cdiv(C, BN_CT), (unsigned)((R + arpc - 1) / arpc)), dim3(256), 0, s, dy, lddy, y, ldy, relu,
-                           x, ldx, running_mean, running_var, eps, scale, shift, C, R, arpc, dx, lddx, dres, lddr, nullptr);
-    } else
-        hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dy, lddy, y, ldy, relu, x, ldx,
-                           running_mean, running_var, eps, scale, shift, C, R, rpc, dx, lddx, dres, lddr, sums ? ws : nullptr);
+    const long rpc = sums ? sp.rpc : apply_rows_per_chunk(C, R);      // element-wise: the finer chunks of the streaming passes
+    const dim3 grid(cdiv(C, BN_CT), (unsigned)((R + rpc - 1) / rpc));
+#define EVAL_BWD(V, SUMS) hipLaunchKernelGGL((bn_eval_bwd_kernel<V, SUMS>), grid, dim3(256), 0, s, dy, lddy, y, ldy, relu, x, ldx, running_mean, running_var, \
+                                             eps, scale, shift, C, R, rpc, dx, lddx, dres, lddr, sums ? ws : nullptr)
+    if (vec) { if (sums) EVAL_BWD(4, true); else EVAL_BWD(4, false); }
+    else { if (sums) EVAL_BWD(1, true); else EVAL_BWD(1, false); }
+#undef EVAL_BWD
     PDF_LAUNCH_CHECK();
     if (sums) {
-        hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, C, dgamma, dbeta, accumulate);
+        hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)sp.chunks, C, dgamma, dbeta, accumulate);
         PDF_LAUNCH_CHECK();
     }
     return 0;
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // Set-abstraction tail (intaghand_encoder.py:59-62,79-82,97-100: BatchNorm2d -> ReLU -> MaxPool2d over the K neighbours) in
@@ -870,22 +596,21 @@ __global__ __launch_bounds__(256) void bn_relu_maxk_fwd_kernel(const float* __re
     }
 }
 // partial sums over the rows r of g = dout * [z > 0] and g * xhat at the selected neighbour (same [chunks][C][2] layout as
-// bn_bwd_partial_v4_kernel, so bn_bwd_finalize_kernel finishes them)
+// bn_bwd_partial_kernel, so bn_bwd_finalize_kernel finishes them)
 __global__ __launch_bounds__(256) void bn_maxk_bwd_partial_kernel(const float* __restrict__ dm, int lddm, const int* __restrict__ arg,
                                                                   const float* __restrict__ y, int ldy, const float* __restrict__ mean,
                                                                   const float* __restrict__ rstd, const float* __restrict__ scale,
                                                                   const float* __restrict__ shift, int C, int K, long R, long rows_per_chunk,
-                                                                  float* __restrict__ part, const BnBwdFin fin) {
-    const long RT = R * K;                                   // the statistics were taken over R*K rows: so are the backward's means
-    __shared__ float4 sa[V4_TY][V4_TX], sb[V4_TY][V4_TX];
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
+                                                                  float* __restrict__ part) {
+    __shared__ vf<4> sa[BN_TY(4)][BN_TX(4)], sb[BN_TY(4)][BN_TX(4)];
+    const int tx = threadIdx.x & (BN_TX(4) - 1), ty = threadIdx.x / BN_TX(4);
     const int c0 = blockIdx.x * BN_CT + tx * 4;
     const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
     if (c0 < C) {
         const float4 m = *reinterpret_cast<const float4*>(mean + c0), rs = *reinterpret_cast<const float4*>(rstd + c0);
         const float4 sc = *reinterpret_cast<const float4*>(scale + c0), sh = *reinterpret_cast<const float4*>(shift + c0);
-        for (long r = r0 + ty; r < r1; r += V4_TY) {
+        for (long r = r0 + ty; r < r1; r += BN_TY(4)) {
             const float4 g4 = *reinterpret_cast<const float4*>(dm + r * lddm + c0);
             const int4 k4 = *reinterpret_cast<const int4*>(arg + r * C + c0);
             const float* base = y + r * K * ldy + c0;
@@ -896,12 +621,7 @@ __global__ __launch_bounds__(256) void bn_maxk_bwd_partial_kernel(const float* _
             b.x += gx * (vx - m.x) * rs.x; b.y += gy * (vy - m.y) * rs.y; b.z += gz * (vz - m.z) * rs.z; b.w += gw * (vw - m.w) * rs.w;
         }
     }
-    v4_block_reduce(a, b, sa, sb, part, C, c0, true, fin.counters != nullptr);
-    if (fin.counters != nullptr) {
-        __shared__ double red[512];
-        __shared__ int flag;
-        if (pdf_last_block_arrives(fin.counters + blockIdx.x, gridDim.y, &flag, false)) bn_bwd_finalize_tile(part, gridDim.y, C, RT, fin, blockIdx.x, red);
-    }
+    bn_block_reduce<4>(as_vf(a), as_vf(b), sa, sb, part, C, c0, true);
 }
 // dy[r][k][c] = a * (g - c1 - xhat * c2), g = dout[r][c] where k == arg[r][c] and the ReLU was active, else 0
 __global__ __launch_bounds__(256) void bn_maxk_bwd_apply_kernel(const float* __restrict__ dm, int lddm, const int* __restrict__ arg,
@@ -946,19 +666,14 @@ static int pdf_bn_relu_maxk_fwd_impl(const float* y, int ldy, int C, long R, int
     if (!v4_ok(C, {ldy, ldo}, {y, out, arg, scale, shift})) return PDF_E_BADARG;
     const long rows = R * K;
     const TileStats ts = {co.tile_stats, co.tile_n, co.tile_rows};
+    const BnFin fin = {gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_rstd, scale, shift};
     if (training && ts.part != nullptr) {
         if (ts.tiles * ts.rows < rows || (ts.tiles - 1) * ts.rows >= rows) return PDF_E_BADARG;
-        hipLaunchKernelGGL(bn_finalize_tiles_kernel, dim3(cdiv(C, FT_C)), dim3(FT_C * FT_L), 0, s, ts.part, (int)ts.tiles, ts.rows, C, rows, gamma, beta,
-                           running_mean, running_var, momentum, eps, save_mean, save_rstd, scale, shift);
+        hipLaunchKernelGGL(bn_finalize_tiles_kernel, dim3(cdiv(C, FT_C)), dim3(FT_C * FT_L), 0, s, ts.part, (int)ts.tiles, ts.rows, C, rows, fin);
     } else if (training) {
-        long chunks = bn_chunks(C, rows);
-        long rpc = (rows + chunks - 1) / chunks;
-        chunks = (rows + rpc - 1) / rpc;
-        BnFin fin = {gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_rstd, scale, shift, bn_inlaunch(C, rows) ? pdf_ticket_counters(cdiv(C, BN_CT)) : nullptr};
-        hipLaunchKernelGGL((bn_partial_v4_kernel<false>), dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, y, ldy, C, rows, rpc, ws, fin);
-        if (fin.counters == nullptr)
-            hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, y, C, rows, gamma, beta,
-                               running_mean, running_var, momentum, eps, save_mean, save_rstd, scale, shift);
+        const BnSplit sp = bn_split(C, rows);
+        hipLaunchKernelGGL((bn_partial_kernel<4, false>), dim3(cdiv(C, BN_CT), (unsigned)sp.chunks), dim3(256), 0, s, y, ldy, C, rows, sp.rpc, ws, (float*)nullptr);
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)sp.chunks, y, C, rows, fin);
     } else {
         hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3(cdiv(C, 128)), dim3(128), 0, s, C, gamma, beta, running_mean, running_var, eps, scale, shift);
     }
@@ -990,15 +705,12 @@ PDF_API int pdf_bn_relu_maxk_bwd(const float* dout, int lddo, const int* arg, co
     hipStream_t s = (hipStream_t)stream;
     if (R <= 0 || C <= 0 || K <= 0) return 0;
     if (!v4_ok(C, {ldy, lddo, lddy}, {y, dout, dy, arg, save_mean, save_rstd, scale, shift, ws})) return PDF_E_BADARG;
-    long chunks = bn_chunks(C, R);
-    long rpc = (R + chunks - 1) / chunks;
-    chunks = (R + rpc - 1) / rpc;
+    const BnSplit sp = bn_split(C, R);
     float* coef = ws + pdf_bn_workspace_floats(C, R);
-    BnBwdFin fin = {gamma, save_rstd, dgamma, dbeta, accumulate, coef, bn_inlaunch(C, R) ? pdf_ticket_counters(cdiv(C, BN_CT)) : nullptr};
-    hipLaunchKernelGGL(bn_maxk_bwd_partial_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dout, lddo, arg, y, ldy, save_mean, save_rstd,
-                       scale, shift, C, K, R, rpc, ws, fin);
-    if (fin.counters == nullptr)      // the statistics were taken over R*K rows: the means of the backward are over R*K as well
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, C, R * K, gamma, save_rstd, dgamma, dbeta, accumulate, coef);
+    hipLaunchKernelGGL(bn_maxk_bwd_partial_kernel, dim3(cdiv(C, BN_CT), (unsigned)sp.chunks), dim3(256), 0, s, dout, lddo, arg, y, ldy, save_mean, save_rstd,
+                       scale, shift, C, K, R, sp.rpc, ws);
+    // the statistics were taken over R*K rows: the means of the backward are over R*K as well
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)sp.chunks, C, R * K, gamma, save_rstd, dgamma, dbeta, accumulate, coef);
     const long total = R * (C / 4);
     hipLaunchKernelGGL(bn_maxk_bwd_apply_kernel, dim3(grid_for(total)), dim3(256), 0, s, dout, lddo, arg, y, ldy, save_mean, save_rstd, coef,
                        scale, shift, C, K, dy, lddy, total);
@@ -1016,8 +728,8 @@ __global__ __launch_bounds__(256) void bn_maxk_eval_bwd_partial_kernel(const flo
                                                                        const float* __restrict__ rvar, float eps, const float* __restrict__ scale,
                                                                        const float* __restrict__ shift, int C, int K, long R, long rows_per_chunk,
                                                                        float* __restrict__ part) {
-    __shared__ float4 sa[V4_TY][V4_TX], sb[V4_TY][V4_TX];
-    const int tx = threadIdx.x & (V4_TX - 1), ty = threadIdx.x / V4_TX;
+    __shared__ vf<4> sa[BN_TY(4)][BN_TX(4)], sb[BN_TY(4)][BN_TX(4)];
+    const int tx = threadIdx.x & (BN_TX(4) - 1), ty = threadIdx.x / BN_TX(4);
     const int c0 = blockIdx.x * BN_CT + tx * 4;
     const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
@@ -1025,7 +737,7 @@ __global__ __launch_bounds__(256) void bn_maxk_eval_bwd_partial_kernel(const flo
         const float4 m = *reinterpret_cast<const float4*>(rmean + c0), var = *reinterpret_cast<const float4*>(rvar + c0);
         const float4 rs = make_float4(1.f / sqrtf(var.x + eps), 1.f / sqrtf(var.y + eps), 1.f / sqrtf(var.z + eps), 1.f / sqrtf(var.w + eps));
         const float4 sc = *reinterpret_cast<const float4*>(scale + c0), sh = *reinterpret_cast<const float4*>(shift + c0);
-        for (long r = r0 + ty; r < r1; r += V4_TY) {
+        for (long r = r0 + ty; r < r1; r += BN_TY(4)) {
             const float4 g4 = *reinterpret_cast<const float4*>(dm + r * lddm + c0);
             const int4 k4 = *reinterpret_cast<const int4*>(arg + r * C + c0);
             const float* base = y + r * K * ldy + c0;
@@ -1036,7 +748,7 @@ __global__ __launch_bounds__(256) void bn_maxk_eval_bwd_partial_kernel(const flo
             b.x += gx * (vx - m.x) * rs.x; b.y += gy * (vy - m.y) * rs.y; b.z += gz * (vz - m.z) * rs.z; b.w += gw * (vw - m.w) * rs.w;
         }
     }
-    v4_block_reduce(a, b, sa, sb, part, C, c0, true);
+    bn_block_reduce<4>(as_vf(a), as_vf(b), sa, sb, part, C, c0, true);
 }
 // dy[r][k][c] = dout[r][c] * scale[c] where k == arg[r][c] and the ReLU was active, else 0
 __global__ __launch_bounds__(256) void bn_maxk_eval_bwd_apply_kernel(const float* __restrict__ dm, int lddm, const int* __restrict__ arg,
@@ -1071,13 +783,11 @@ PDF_API int pdf_bn_relu_maxk_eval_bwd(const float* dout, int lddo, const int* ar
     if (sums && (running_mean == nullptr || running_var == nullptr || ws == nullptr)) return PDF_E_BADARG;
     if (!v4_ok(C, {ldy, lddo, dy ? lddy : 0}, {y, dout, dy, arg, scale, shift, sums ? running_mean : nullptr, sums ? running_var : nullptr})) return PDF_E_BADARG;
     if (sums) {
-        long chunks = bn_chunks(C, R);
-        long rpc = (R + chunks - 1) / chunks;
-        chunks = (R + rpc - 1) / rpc;
-        hipLaunchKernelGGL(bn_maxk_eval_bwd_partial_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks), dim3(256), 0, s, dout, lddo, arg, y, ldy,
-                           running_mean, running_var, eps, scale, shift, C, K, R, rpc, ws);
+        const BnSplit sp = bn_split(C, R);
+        hipLaunchKernelGGL(bn_maxk_eval_bwd_partial_kernel, dim3(cdiv(C, BN_CT), (unsigned)sp.chunks), dim3(256), 0, s, dout, lddo, arg, y, ldy,
+                           running_mean, running_var, eps, scale, shift, C, K, R, sp.rpc, ws);
         PDF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, C, dgamma, dbeta, accumulate);
+        hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(cdiv(C, FIN_TX)), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)sp.chunks, C, dgamma, dbeta, accumulate);
         PDF_LAUNCH_CHECK();
     }
     if (dy != nullptr) {
@@ -1100,35 +810,33 @@ __global__ __launch_bounds__(FIN_TX * FIN_TY) void colsum_finalize_kernel(const 
     out[c] = (accumulate ? out[c] : 0.f) + (float)a;
 }
 
+// (blockIdx.z == 1 is group 1 of a paired call -- rows [R, 2R), partials after group 0's)
+template <int V>
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ g, int ldg, int C, long R, long rows_per_chunk, float* __restrict__ part) {
-    __shared__ float s1[4][BN_CT];
+    __shared__ vf<V> sa[BN_TY(V)][BN_TX(V)], sb[BN_TY(V)][BN_TX(V)];
     if (blockIdx.z) { g += R * ldg; part += (long)gridDim.y * C * 2; }
-    const int tx = threadIdx.x & (BN_CT - 1), ty = threadIdx.x / BN_CT;
-    const int c = blockIdx.x * BN_CT + tx;
-    const long r0 = blockIdx.y * rows_per_chunk;
-    const long r1 = min(R, r0 + rows_per_chunk);
-    float a = 0.f;
-    if (c < C) for (long r = r0 + ty; r < r1; r += 4) a += g[r * ldg + c];
-    s1[ty][tx] = a;
-    __syncthreads();
-    if (ty == 0 && c < C) {
-        part[((long)blockIdx.y * C + c) * 2] = s1[0][tx] + s1[1][tx] + s1[2][tx] + s1[3][tx];
-        part[((long)blockIdx.y * C + c) * 2 + 1] = 0.f;
+    const int tx = threadIdx.x & (BN_TX(V) - 1), ty = threadIdx.x / BN_TX(V);
+    const int c0 = blockIdx.x * BN_CT + tx * V;
+    const long r0 = blockIdx.y * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
+    vf<V> a = {};
+    if (c0 < C) {
+#pragma unroll 4
+        for (long r = r0 + ty; r < r1; r += BN_TY(V)) a += vld<V>(g + r * ldg + c0);
     }
+    bn_block_reduce<V>(a, a, sa, sb, part, C, c0, false);
 }
 
 static int colsum_launch(const float* g, int ldg, int C, long R, float* out, float* out1, int accumulate, float* ws, hipStream_t s) {
     if (R <= 0 || C <= 0) return 0;
     const unsigned groups = out1 ? 2 : 1;
-    long chunks = bn_chunks(C, R);
-    long rpc = (R + chunks - 1) / chunks;
-    chunks = (R + rpc - 1) / rpc;
+    const BnSplit sp = bn_split(C, R);
+    const dim3 grid(cdiv(C, BN_CT), (unsigned)sp.chunks, groups);
     if (v4_ok(C, {ldg, (int)((R * ldg) % 4)}, {g}))
-        hipLaunchKernelGGL(colsum_partial_v4_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks, groups), dim3(256), 0, s, g, ldg, C, R, rpc, ws);
+        hipLaunchKernelGGL(colsum_partial_kernel<4>, grid, dim3(256), 0, s, g, ldg, C, R, sp.rpc, ws);
     else
-        hipLaunchKernelGGL(colsum_partial_kernel, dim3(cdiv(C, BN_CT), (unsigned)chunks, groups), dim3(256), 0, s, g, ldg, C, R, rpc, ws);
+        hipLaunchKernelGGL(colsum_partial_kernel<1>, grid, dim3(256), 0, s, g, ldg, C, R, sp.rpc, ws);
     PDF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cdiv(C, FIN_TX), groups), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)chunks, C, out, out1, accumulate);
+    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cdiv(C, FIN_TX), groups), dim3(FIN_TX, FIN_TY), 0, s, ws, (int)sp.chunks, C, out, out1, accumulate);
     PDF_LAUNCH_CHECK();
     return 0;
 }

@@ -136,7 +136,10 @@ def test_deconv2d(F, cfg):
 
 
 @pytest.mark.parametrize("shape,relu,res", [((4, 64, 9, 9), True, False), ((2, 256, 8, 8), True, True), ((3, 3, 5, 5), False, False),
-                                            ((700, 130), True, False), ((2, 128, 31, 33), False, True)])
+                                            ((700, 130), True, False), ((2, 128, 31, 33), False, True),
+                                            # scalar form (C % 4 != 0): mask from y with dres written; a second channel tile of two channels
+                                            # with the mask recomputed from x.  float4 form whose second channel tile holds a single quad
+                                            ((3, 6, 5, 5), True, True), ((2, 66, 3, 3), True, False), ((2, 68, 6, 6), True, True)])
 def test_batchnorm(F, shape, relu, res):
     C = shape[1]
     x = rnd(*shape, seed=1) * 2 + 0.5

@@ -52,8 +52,8 @@ def load(d, counter, by_tile=False):
 
 
 HBM_KERNELS = ("knn_ball_group_kernel", "gather_sub_fwd_kernel", "gather_sub_bwd_kernel", "gather_sub_bwd_du_kernel", "gather_sub_bwd_dv_kernel", "invert_index_kernel", "bn_relu_maxk_fwd_kernel", "bn_maxk_bwd_partial_kernel",
-               "bn_maxk_bwd_apply_kernel", "gather_rows_kernel", "scatter_rows_kernel", "bn_partial_v4_kernel", "affine_apply_v4_kernel",
-               "bn_bwd_partial_v4_kernel", "bn_bwd_apply_v4_kernel", "l2norm_fwd_kernel", "l2norm_bwd_kernel", "l2norm_cat_fwd_kernel", "l2norm_cat_bwd_kernel", "up2_fwd_v4_kernel", "up2_bwd_v4_kernel",
+               "bn_maxk_bwd_apply_kernel", "gather_rows_kernel", "scatter_rows_kernel", "bn_partial_kernel", "affine_apply_kernel",
+               "bn_bwd_partial_kernel", "bn_bwd_apply_kernel", "l2norm_fwd_kernel", "l2norm_bwd_kernel", "l2norm_cat_fwd_kernel", "l2norm_cat_bwd_kernel", "up2_fwd_v4_kernel", "up2_bwd_v4_kernel",
                "adam_kernel", "fps_kernel", "maxk_fwd_kernel", "maxk_bwd_kernel", "group_bwd_kernel")
 POINTNET = HBM_KERNELS[:11]
 
