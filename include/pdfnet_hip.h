@@ -431,6 +431,34 @@ int pdf_mesh_nn_counts(const float* pred, const float* gt, int rows, int n, cons
 int pdf_mesh_penetration(const float* verts, const long long* faces, int B, int n, int Fc,
                          float* wind, float* dist, int* count, float* depth, float* gap, void* stream);
 
+/* ---- ICP refinement against the sensor point cloud (csrc/icp.hip) ------------------------------- */
+/* Row (b, h): the mesh of hand h of sample b is moved, rigidly or by a translation alone, onto that hand's sensor point cloud by `iters`
+ * iterations of trimmed point-to-surface ICP.  Forward only.
+ * verts [B,2,n,3] f32 camera-space metres (left, right); faces [2,Fc,3] int64, the tensor pdf_mesh_penetration takes, both hands oriented
+ * outwards (an index outside [0, n) is clamped); cloud [B,2,P,3] f32 camera-space metres (pdf_depth2pcl's): a point with Z <= 0 is ignored, so
+ * the all-zero cloud of an absent hand matches nothing; valid [B,2] f32 or NULL.
+ * Association, for every point p that is not ignored: q = the closest point of the current mesh's surface, over the triangles that face the
+ * camera at the origin: n . (a + b + c) < 0 with n = (b - a) x (c - a), so a zero-area triangle (n = 0) is never matched.  q by the seven
+ * regions of the point-to-triangle distance, tested in the order vertex a, vertex b, edge ab, vertex c, edge ac, edge bc, face; among equal
+ * distances the lowest face index wins.  p is an inlier when |p - q| < trim, strictly.  fp32.
+ * Update k, from the inliers' sums in double:  rigid == 0: R_k = I, t_k = mean (p - q); without an inlier the iteration stops.
+ *   rigid != 0: the rotation with det = +1 and the translation that minimise sum |R_k q + t_k - p|^2 (Kabsch: H = sum (q - mean q)(p - mean p)^T
+ *   = U S V^T, R_k = V diag(1, 1, det(V U^T)) U^T, t_k = mean p - R_k mean q); when the second singular value of H is below 1e-6 of the largest,
+ *   that iteration takes R_k = I, t_k = mean p - mean q; with fewer than 3 inliers the iteration stops.
+ *   (R, t) <- (R_k R, R_k t + t_k) in double, and the current mesh becomes the fp32 rounding of R v + t of the ORIGINAL vertices.
+ * After `iters` updates (or the stop) one more association of the result gives
+ *   inliers [B,2] int32 and rms [B,2] f32: the root mean square of |p - q| over the inliers, 0 without any;
+ *   closest [B,2,P,3] f32 or NULL: q, and tri [B,2,P] int32 or NULL: its face index; (0, 0, 0) and -1 for an ignored point and when no
+ *   triangle faces the camera.
+ *   out_verts [B,2,n,3] or NULL: the moved mesh; R [B,2,3,3] row-major and t [B,2,3], or NULL: out = R v + t about the camera origin.
+ * iters = 0 is the association alone (the cloud-to-mesh residual).  A hand with valid = 0 or without a point that is not ignored keeps its
+ * vertices, R = I, t = 0, rms = 0, inliers = 0, closest = 0, tri = -1.
+ * 1 <= n <= 1024, 1 <= Fc <= 2048, 1 <= P <= 1024, 0 <= iters <= 64, trim > 0 and finite, else PDF_E_BADARG with nothing launched; B <= 0
+ * returns 0.  Finite input gives finite output: no quotient has a denominator that can be zero.  One launch, one workgroup per row, no atomics,
+ * no scratch memory: two runs are bit-identical and a row's result does not depend on the other rows of the batch. */
+int pdf_mesh_icp(const float* verts, const long long* faces, const float* cloud, const float* valid, int B, int n, int Fc, int P, int iters,
+                 float trim, int rigid, float* out_verts, float* R, float* t, float* rms, int* inliers, float* closest, int* tri, void* stream);
+
 /* ---- hand renderer (csrc/render.hip) ------------------------------------------------------------ */
 /* Forward-only z-buffered rasteriser of both hands of every sample under that sample's pinhole camera (the reference's pytorch3d
  * MeshRasterizer + HardPhongShader, lib/models/networks/mano_utils.py:44-156).  The arithmetic contract -- pixel (i, j) sampled at

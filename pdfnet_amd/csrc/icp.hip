@@ -1,0 +1,274 @@
+// ICP refinement of a predicted hand mesh against that hand's sensor point cloud (contract: pdf_mesh_icp in pdfnet_hip.h).  Nothing in the
+// reference does this: its pipeline never looks at the depth measurement again once the mesh is out.
+//
+// One launch for the whole loop, one workgroup of 1,024 lanes per row = (sample, hand), lane t owns cloud point t and vertex t.
+//   LDS: the hand's CURRENT vertices as x / y / z planes (12 KB), its faces as 16-bit triples (16 KB), and the list of the camera-facing
+//   triangles of the current mesh as their three corners, 48 B a triangle (96 KB), rebuilt before every association: lane t tests face
+//   base + t, the survivors are compacted in face order by a 64-bit __ballot + popcount prefix per wave and the wave totals through LDS
+//   (render_tile_kernel's idiom).  The walk reads the list front to back, every lane the same triangle: three broadcast 16-byte reads and no
+//   index to chase.
+//   Association: closest point by the seven regions (Ericson, Real-Time Collision Detection 5.1.5), tested in the order vertex A, vertex B,
+//   edge AB, vertex C, edge AC, edge BC, face; fp32; a strictly smaller squared distance replaces the best, so the lowest face index wins a tie.
+//   Every quotient has its denominator held at or above ICP_TINY.
+//   Update: count, sum p, sum q, sum q p^T and sum |p - q|^2 over the inliers as doubles: xor butterfly per wave, the 16 wave partials through
+//   LDS, added by lane 0 as a balanced tree.  Lane 0 solves (svd3.h) and composes the step into (R, t), kept in double in LDS; every lane then
+//   rewrites its vertex of the LDS copy as fp32(R v0 + t) from the ORIGINAL vertex it holds in registers, so rounding does not pile up over
+//   the iterations and out_verts is exactly the fp32 rounding of R v + t.
+// No atomics, no global scratch: two runs are bit-identical and a row does not depend on the other rows of the batch.
+#include "common.h"
+#include "svd3.h"
+
+#define ICP_T 1024
+#define ICP_W (ICP_T / 64)
+#define ICP_MAXN 1024
+#define ICP_MAXF 2048
+#define ICP_MAXP 1024
+#define ICP_MAXIT 64
+#define ICP_TINY 1e-37f
+#define ICP_K 17                                               // count, sum p [3], sum q [3], sum q p^T [9], sum |p - q|^2
+
+// p q - r s from separately rounded products (no fma): the normal of a triangle with two equal corners, or with collinear corners whose
+// edges are exact multiples of each other, is exactly zero
+__device__ __forceinline__ float icp_det2(float p, float q, float r, float s) {
+#pragma clang fp contract(off)
+    return p * q - r * s;
+}
+
+struct IcpShared {                                             // (the small members first: their addresses fit a DS instruction's 16-bit offset)
+    double red[ICP_W * ICP_K], sum[ICP_K];                     // wave partials; the inlier sums of the last association
+    double xf[12];                                             // R row-major, then t
+    double svd[4][3][3];                                       // the one-lane solve works here, not in registers: H, G, U, V
+    int wave_n[ICP_W];
+    int stop;
+    float vx[ICP_MAXN], vy[ICP_MAXN], vz[ICP_MAXN];
+    ushort4 tri[ICP_MAXF];
+    float4 ca[ICP_MAXF], cb[ICP_MAXF], cc[ICP_MAXF];           // corners of the camera-facing triangles; ca.w carries the face index
+};
+
+// the camera-facing triangles of the current LDS mesh -> s.ca / cb / cc in face order; returns their number (block-uniform)
+__device__ __forceinline__ int icp_facing(IcpShared& s, int Fc) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int total = 0;
+    for (int base = 0; base < Fc; base += ICP_T) {
+        const int g = base + t;
+        bool keep = false;
+        float ax = 0.f, ay = 0.f, az = 0.f, bx = 0.f, by = 0.f, bz = 0.f, cx = 0.f, cy = 0.f, cz = 0.f;
+        if (g < Fc) {
+            const ushort4 f = s.tri[g];
+            ax = s.vx[f.x]; ay = s.vy[f.x]; az = s.vz[f.x];
+            bx = s.vx[f.y]; by = s.vy[f.y]; bz = s.vz[f.y];
+            cx = s.vx[f.z]; cy = s.vy[f.z]; cz = s.vz[f.z];
+            const float e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
+            const float nx = icp_det2(e1y, e2z, e1z, e2y), ny = icp_det2(e1z, e2x, e1x, e2z), nz = icp_det2(e1x, e2y, e1y, e2x);
+            keep = nx * (ax + bx + cx) + ny * (ay + by + cy) + nz * (az + bz + cz) < 0.f;
+        }
+        const unsigned long long mask = __ballot(keep);
+        if (lane == 0) s.wave_n[wave] = __popcll(mask);
+        __syncthreads();
+        int off = total + __popcll(mask & ((1ULL << lane) - 1ULL));
+#pragma unroll
+        for (int w = 0; w < ICP_W; ++w) {
+            const int c = s.wave_n[w];
+            if (w < wave) off += c;
+            total += c;
+        }
+        if (keep) {                                            // off < total <= base + ICP_T, at most Fc <= ICP_MAXF
+            s.ca[off] = make_float4(ax, ay, az, __int_as_float(g));
+            s.cb[off] = make_float4(bx, by, bz, 0.f);
+            s.cc[off] = make_float4(cx, cy, cz, 0.f);
+        }
+        __syncthreads();                                       // wave_n is rewritten by the next chunk; the list is read after the last one
+    }
+    return total;
+}
+
+// closest point of the listed triangles to (px, py, pz): squared distance, the point and the face index (-1: the list is empty)
+__device__ __forceinline__ void icp_walk(const IcpShared& s, int count, float px, float py, float pz, float& best, float& qx, float& qy, float& qz,
+                                         int& face) {
+    best = 3.0e38f; qx = qy = qz = 0.f; face = -1;
+    for (int j = 0; j < count; ++j) {
+        const float4 a = s.ca[j], b = s.cb[j], c = s.cc[j];
+        const float abx = b.x - a.x, aby = b.y - a.y, abz = b.z - a.z, acx = c.x - a.x, acy = c.y - a.y, acz = c.z - a.z;
+        const float apx = px - a.x, apy = py - a.y, apz = pz - a.z;
+        const float bpx = px - b.x, bpy = py - b.y, bpz = pz - b.z;
+        const float cpx = px - c.x, cpy = py - c.y, cpz = pz - c.z;
+        const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
+        const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
+        const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
+        const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+        // q = a + v ab + w ac; the face first, then the regions from the last of the order to the first, so the first that holds wins
+        const float inv = __frcp_rn(fmaxf(va + vb + vc, ICP_TINY));
+        float v = fminf(fmaxf(vb * inv, 0.f), 1.f), w = fminf(fmaxf(vc * inv, 0.f), 1.f);
+        if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) {                                   // edge BC
+            w = fminf((d4 - d3) * __frcp_rn(fmaxf((d4 - d3) + (d5 - d6), ICP_TINY)), 1.f);
+            v = 1.f - w;
+        }
+        if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { v = 0.f; w = fminf(d2 * __frcp_rn(fmaxf(d2 - d6, ICP_TINY)), 1.f); }      // edge AC
+        if (d6 >= 0.f && d5 <= d6) { v = 0.f; w = 1.f; }                                       // vertex C
+        if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { v = fminf(d1 * __frcp_rn(fmaxf(d1 - d3, ICP_TINY)), 1.f); w = 0.f; }      // edge AB
+        if (d3 >= 0.f && d4 <= d3) { v = 1.f; w = 0.f; }                                       // vertex B
+        if (d1 <= 0.f && d2 <= 0.f) { v = 0.f; w = 0.f; }                                      // vertex A
+        const float rx = v * abx + w * acx - apx, ry = v * aby + w * acy - apy, rz = v * abz + w * acz - apz;      // q - p
+        const float dd = rx * rx + ry * ry + rz * rz;
+        if (dd < best) { best = dd; qx = px + rx; qy = py + ry; qz = pz + rz; face = __float_as_int(a.w); }
+    }
+}
+
+// v[0..ICP_K) summed over the block in a fixed order -> out[0..ICP_K) in LDS (ends in a barrier): the xor butterfly per wave, then thread k
+// adds the 16 wave partials of sum k as a balanced tree
+__device__ __forceinline__ void icp_block_sum(double* v, double* sm, double* out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < ICP_K; ++k) {
+        const double r = wave_sum_d(v[k]);
+        if (lane == 0) sm[wave * ICP_K + k] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < ICP_K) {
+        double p[ICP_W];
+#pragma unroll
+        for (int w = 0; w < ICP_W; ++w) p[w] = sm[w * ICP_K + threadIdx.x];
+#pragma unroll
+        for (int m = ICP_W / 2; m > 0; m /= 2) {
+#pragma unroll
+            for (int w = 0; w < m; ++w) p[w] = p[2 * w] + p[2 * w + 1];
+        }
+        out[threadIdx.x] = p[0];
+    }
+    __syncthreads();
+}
+
+// One step from the inlier sums a[]: composes it into xf (R row-major, t).  Returns false when the iteration stops.
+__device__ __forceinline__ bool icp_step(const double* a, int rigid, double* xf, double (*ws)[3][3]) {
+    const double N = a[0];
+    if (N < (rigid ? 3.0 : 1.0)) return false;
+    const double pm[3] = {a[1] / N, a[2] / N, a[3] / N}, qm[3] = {a[4] / N, a[5] / N, a[6] / N};
+    double Rk[3][3];
+    bool full = false;
+    if (rigid) {
+        double (*H)[3] = ws[0], (*u)[3] = ws[2], (*v)[3] = ws[3], sg[3];      // H = sum (q - qm)(p - pm)^T = U S V^T; R_k = V diag(1, 1, d) U^T
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) H[r][c] = a[7 + 3 * r + c] - N * qm[r] * pm[c];
+        if (met_svd_3x3(H, ws[1], u, v, sg) && sg[1] >= 1e-6 * sg[0]) {
+            full = true;
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) Rk[r][c] = v[0][r] * u[0][c] + v[1][r] * u[1][c] + v[2][r] * u[2][c];
+            const double det = Rk[0][0] * (Rk[1][1] * Rk[2][2] - Rk[1][2] * Rk[2][1]) - Rk[0][1] * (Rk[1][0] * Rk[2][2] - Rk[1][2] * Rk[2][0]) +
+                               Rk[0][2] * (Rk[1][0] * Rk[2][1] - Rk[1][1] * Rk[2][0]);
+            if (det < 0.0)                                     // d = -1: the weakest direction changes sign
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 3; ++c) Rk[r][c] -= 2.0 * v[2][r] * u[2][c];
+        }
+    }
+    if (!full)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) Rk[r][c] = r == c ? 1.0 : 0.0;
+    double tk[3], Rn[3][3], tn[3];
+    for (int r = 0; r < 3; ++r) tk[r] = pm[r] - (Rk[r][0] * qm[0] + Rk[r][1] * qm[1] + Rk[r][2] * qm[2]);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Rn[r][c] = Rk[r][0] * xf[c] + Rk[r][1] * xf[3 + c] + Rk[r][2] * xf[6 + c];
+        tn[r] = Rk[r][0] * xf[9] + Rk[r][1] * xf[10] + Rk[r][2] * xf[11] + tk[r];
+    }
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) xf[3 * r + c] = Rn[r][c];
+        xf[9 + r] = tn[r];
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(ICP_T) void mesh_icp_kernel(const float* __restrict__ verts, const long long* __restrict__ faces,
+                                                         const float* __restrict__ cloud, const float* __restrict__ valid, int n, int Fc, int P,
+                                                         int iters, float trim, int rigid, float* __restrict__ out_verts, float* __restrict__ R,
+                                                         float* __restrict__ tr, float* __restrict__ rms, int* __restrict__ inliers,
+                                                         float* __restrict__ closest, int* __restrict__ tri) {
+    __shared__ IcpShared s;
+    const int t = threadIdx.x;
+    const long row = blockIdx.x;
+    const int h = (int)(row & 1);
+    // The lane's point and its original vertex are read again where they are used (12 bytes each, from L2) instead of being held across the
+    // one-lane solve, which needs the registers: the kernel must fit 128 VGPRs without scratch.
+    const float* pp = cloud + (row * P + min(t, P - 1)) * 3;
+    const float* vp = verts + (row * n + min(t, n - 1)) * 3;
+    const bool live = t < P && pp[2] > 0.f;
+    const bool row_ok = valid == nullptr || valid[row] != 0.f;
+    if (!__syncthreads_or(live && row_ok)) {                   // block-uniform: the hand stays where it is
+        if (t < n && out_verts != nullptr) { float* o = out_verts + (row * n + t) * 3; o[0] = vp[0]; o[1] = vp[1]; o[2] = vp[2]; }
+        if (t < 9 && R != nullptr) R[row * 9 + t] = t % 4 == 0 ? 1.f : 0.f;
+        if (t < 3 && tr != nullptr) tr[row * 3 + t] = 0.f;
+        if (t == 0) { rms[row] = 0.f; inliers[row] = 0; }
+        if (t < P) {
+            if (closest != nullptr) { float* c = closest + (row * P + t) * 3; c[0] = c[1] = c[2] = 0.f; }
+            if (tri != nullptr) tri[row * P + t] = -1;
+        }
+        return;
+    }
+    if (t < n) { s.vx[t] = vp[0]; s.vy[t] = vp[1]; s.vz[t] = vp[2]; }
+    const long long* fo = faces + (long)h * Fc * 3;
+    for (int g = t; g < Fc; g += ICP_T) {
+        ushort4 f;                                             // an index outside [0, n) is clamped: it must not leave the staged planes
+        f.x = (unsigned short)min(max(fo[3 * g + 0], 0LL), (long long)(n - 1));
+        f.y = (unsigned short)min(max(fo[3 * g + 1], 0LL), (long long)(n - 1));
+        f.z = (unsigned short)min(max(fo[3 * g + 2], 0LL), (long long)(n - 1));
+        f.w = 0;
+        s.tri[g] = f;
+    }
+    if (t < 12) s.xf[t] = t < 9 && t % 4 == 0 ? 1.0 : 0.0;
+    if (t == 0) s.stop = 0;
+    __syncthreads();
+
+    float best, qx, qy, qz;
+    int face;
+    for (int it = 0; ; ++it) {
+        const int count = icp_facing(s, Fc);                   // (ends in a barrier)
+        const float px = pp[0], py = pp[1], pz = pp[2];
+        best = 3.0e38f; qx = qy = qz = 0.f; face = -1;
+        if (__ballot(live) != 0ULL) icp_walk(s, count, px, py, pz, best, qx, qy, qz, face);      // wave-uniform; a dead lane's result is not used
+        const bool in = live && face >= 0 && sqrtf(best) < trim;
+        const double dpx = in ? px : 0.f, dpy = in ? py : 0.f, dpz = in ? pz : 0.f, dqx = in ? qx : 0.f, dqy = in ? qy : 0.f, dqz = in ? qz : 0.f;
+        double a[ICP_K];
+        a[0] = in ? 1.0 : 0.0; a[1] = dpx; a[2] = dpy; a[3] = dpz; a[4] = dqx; a[5] = dqy; a[6] = dqz;
+        a[7] = dqx * dpx; a[8] = dqx * dpy; a[9] = dqx * dpz; a[10] = dqy * dpx; a[11] = dqy * dpy; a[12] = dqy * dpz;
+        a[13] = dqz * dpx; a[14] = dqz * dpy; a[15] = dqz * dpz;
+        a[16] = in ? (double)best : 0.0;
+        icp_block_sum(a, s.red, s.sum);
+        if (it == iters) break;                                // the final association: s.sum feeds rms and inliers
+        if (t == 0 && !icp_step(s.sum, rigid, s.xf, s.svd)) s.stop = 1;
+        __syncthreads();
+        if (s.stop) {                                          // block-uniform.  The mesh did not move: this association is the final one
+            break;
+        }
+        if (t < n) {
+            const double x = vp[0], y = vp[1], z = vp[2];
+            s.vx[t] = (float)(s.xf[0] * x + s.xf[1] * y + s.xf[2] * z + s.xf[9]);
+            s.vy[t] = (float)(s.xf[3] * x + s.xf[4] * y + s.xf[5] * z + s.xf[10]);
+            s.vz[t] = (float)(s.xf[6] * x + s.xf[7] * y + s.xf[8] * z + s.xf[11]);
+        }
+        __syncthreads();
+    }
+    if (t < n && out_verts != nullptr) { float* o = out_verts + (row * n + t) * 3; o[0] = s.vx[t]; o[1] = s.vy[t]; o[2] = s.vz[t]; }
+    if (t < 9 && R != nullptr) R[row * 9 + t] = (float)s.xf[t];
+    if (t < 3 && tr != nullptr) tr[row * 3 + t] = (float)s.xf[9 + t];
+    if (t == 0) {
+        rms[row] = s.sum[0] > 0.0 ? (float)sqrt(s.sum[16] / s.sum[0]) : 0.f;
+        inliers[row] = (int)s.sum[0];
+    }
+    if (t < P) {
+        const bool hit = live && face >= 0;
+        if (closest != nullptr) { float* c = closest + (row * P + t) * 3; c[0] = hit ? qx : 0.f; c[1] = hit ? qy : 0.f; c[2] = hit ? qz : 0.f; }
+        if (tri != nullptr) tri[row * P + t] = hit ? face : -1;
+    }
+}
+
+PDF_API int pdf_mesh_icp(const float* verts, const long long* faces, const float* cloud, const float* valid, int B, int n, int Fc, int P, int iters,
+                         float trim, int rigid, float* out_verts, float* R, float* t, float* rms, int* inliers, float* closest, int* tri,
+                         void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (n < 1 || n > ICP_MAXN || Fc < 1 || Fc > ICP_MAXF || P < 1 || P > ICP_MAXP || iters < 0 || iters > ICP_MAXIT || !(trim > 0.f) ||
+        !(trim <= 3.0e38f) || verts == nullptr || faces == nullptr || cloud == nullptr || rms == nullptr || inliers == nullptr)
+        return PDF_E_BADARG;
+    hipLaunchKernelGGL(mesh_icp_kernel, dim3(2 * B), dim3(ICP_T), 0, s, verts, faces, cloud, valid, n, Fc, P, iters, trim, rigid, out_verts, R, t,
+                       rms, inliers, closest, tri);
+    PDF_LAUNCH_CHECK();
+    return 0;
+}

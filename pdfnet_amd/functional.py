@@ -2450,6 +2450,43 @@ def mesh_penetration(verts, faces, return_fields=False):
     return (count, depth, gap, wind, dist) if return_fields else (count, depth, gap)
 
 
+def mesh_icp(verts, faces, cloud, valid=None, iters=8, trim=0.03, rigid=False, return_fields=False):
+    """verts [..., 2, n, 3] camera-space metres (left, right hand), faces [2, Fc, 3] int64 (the loss module's `faces_pair`, oriented outwards),
+    cloud [..., 2, P, 3] that hand's sensor points in camera-space metres (`depth2pcl`'s; a point with Z <= 0 is ignored), valid [..., 2] or
+    None -> (verts_refined [..., 2, n, 3], R [..., 2, 3, 3], t [..., 2, 3], rms [..., 2], inliers int32 [..., 2]): each hand moved onto its
+    cloud by `iters` iterations of trimmed ICP against the camera-facing surface of its own mesh -- a translation per iteration, or with
+    `rigid` the Kabsch rotation and translation -- with verts_refined = R v + t; rms and inliers are the root mean square distance and the number
+    of the points closer than `trim` to the refined surface.  iters = 0 moves nothing: rms is the cloud-to-mesh residual of the input.
+    return_fields: also (closest [..., 2, P, 3], tri int32 [..., 2, P]), each point's closest surface point and its face, (0, 0, 0) and -1
+    where there is none.  A hand with valid = 0 or without a usable point comes back unchanged with R = I, t = 0, rms = 0, inliers = 0.
+    The contract is `pdf_mesh_icp`'s in pdfnet_hip.h.  n, P <= 1024, Fc <= 2048, iters <= 64.  No gradient; deterministic."""
+    hip.require_gpu(verts, faces, cloud, valid)
+    v, f, c = verts.detach().float().contiguous(), faces.detach().long().contiguous(), cloud.detach().float().contiguous()
+    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
+        raise ValueError("pdfnet_amd: mesh_icp wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
+    lead, n, Fc = v.shape[:-2], v.shape[-2], f.shape[1]
+    if c.dim() != v.dim() or c.shape[:-2] != lead or c.shape[-1] != 3:
+        raise ValueError("pdfnet_amd: mesh_icp wants cloud %s for verts %s, got %s" % (tuple(lead) + ('P', 3), tuple(v.shape), tuple(c.shape)))
+    P, iters, trim = c.shape[-2], int(iters), float(trim)
+    if not (1 <= n <= 1024 and 1 <= Fc <= 2048 and 1 <= P <= 1024):
+        raise ValueError("pdfnet_amd: mesh_icp takes 1 to 1024 vertices, 1 to 2048 faces and 1 to 1024 points per hand, got %d, %d and %d" % (n, Fc, P))
+    if not (0 <= iters <= 64 and 0.0 < trim < float('inf')):
+        raise ValueError("pdfnet_amd: mesh_icp takes 0 to 64 iterations and a finite trim > 0, got %r and %r" % (iters, trim))
+    va = None
+    if valid is not None:
+        va = valid.detach().float().contiguous()
+        if va.shape != lead:
+            raise ValueError("pdfnet_amd: mesh_icp wants valid %s, got %s" % (tuple(lead), tuple(va.shape)))
+    dev = v.device
+    out, R, t = torch.empty_like(v), torch.empty(lead + (3, 3), dtype=torch.float32, device=dev), torch.empty(lead + (3,), dtype=torch.float32, device=dev)
+    rms, inliers = torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev)
+    closest = torch.empty_like(c) if return_fields else None
+    tri = torch.empty(lead + (P,), dtype=torch.int32, device=dev) if return_fields else None
+    _L().pdf_mesh_icp(ptr(v), ptr(f), ptr(c), ptr(va), rms.numel() // 2, n, Fc, P, iters, trim, int(bool(rigid)), ptr(out), ptr(R), ptr(t), ptr(rms),
+                      ptr(inliers), ptr(closest), ptr(tri), stream())
+    return (out, R, t, rms, inliers, closest, tri) if return_fields else (out, R, t, rms, inliers)
+
+
 # ----------------------------------------------------------------------------------------------
 # Hand renderer (csrc/render.hip): the reference's pytorch3d MeshRasterizer + HardPhongShader (mano_utils.py:44-156) as a tile rasteriser.
 RENDER_MAX_DEGREE = 32

@@ -622,7 +622,7 @@ class Trainer:
         return tot / max(n, 1)
 
 
-    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False, rendered=False):
+    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False, rendered=False, refined=False):
         """Counterpart of `BaseTrainer.evaluation` (lib/trains/base_trainer.py:207-429, H2O branch): the test-mode pass
         (centres from the predicted heat-map, root from the predicted depth) and the mean Euclidean errors per hand --
         absolute and root-relative joints / vertices in mm, 2-D landmarks in pixels.  The reference evaluates on rank 0
@@ -645,7 +645,13 @@ class Trainer:
         rendered:   also the agreement in the image plane: the predicted and the ground-truth absolute meshes are rendered under
                     batch['K_new'] at the input's resolution (`F.render_hands`) and compared (`F.render_compare`): silhouette IoU per hand, and the
                     mean |rendered Z - sensor Z| over the pixels the prediction covers when the batch carries its `depth` map -- the keys of
-                    `finish_rendered`.  One more accumulator in the same buffer; needs `faces_pair`.  The other keys do not change."""
+                    `finish_rendered`.  One more accumulator in the same buffer; needs `faces_pair`.  The other keys do not change.
+        refined:    False, True (= 'translation') or 'rigid': also what the depth measurement can still correct -- each predicted hand is moved
+                    onto its sensor point cloud batch['cloud'] [B, 2, P, 3] (camera-space metres, `F.depth2pcl`'s) by `F.mesh_icp`, with a
+                    translation or a rigid motion per iteration, and the absolute errors are taken again: the keys of `finish_refined`.  One
+                    more accumulator in the same buffer; needs `faces_pair`.  The other keys do not change."""
+        if refined not in (False, True, 'translation', 'rigid'):
+            raise ValueError("Trainer.evaluation: refined is False, True, 'translation' or 'rigid', got %r" % (refined,))
         mwl = self.model_with_loss
         was_training = mwl.training
         mwl.eval()
@@ -661,6 +667,8 @@ class Trainer:
                 acc3 = torch.zeros(12, dtype=torch.float64, device=dev)   # see interaction_sums
             if rendered:
                 acc4 = torch.zeros(8, dtype=torch.float64, device=dev)    # see rendered_sums
+            if refined:
+                acc5 = torch.zeros(REFINED_SUMS, dtype=torch.float64, device=dev)      # see refined_sums
             poses = []
             with torch.no_grad():
                 for batch in loader:
@@ -675,6 +683,8 @@ class Trainer:
                         acc3 += interaction_sums(tup, batch, mwl.loss.faces_pair)
                     if rendered:
                         acc4 += rendered_sums(tup, batch, mwl.loss.faces_pair)
+                    if refined:
+                        acc5 += refined_sums(tup, batch, mwl.loss.faces_pair, refined == 'rigid')
                     if json_path is not None:
                         if 'id' not in batch or 'frame_num' not in batch:
                             raise KeyError("Trainer.evaluation: hand_poses.json needs batch['id'] and batch['frame_num'] (interhand.py H2O entries)")
@@ -684,7 +694,10 @@ class Trainer:
                         poses.append(torch.cat((key, jp.reshape(jp.shape[0], -1).double()), 1))          # [B, 2 + 126]
             if aligned:                                            # one buffer for the reduction and the copy (the counts are exact in float64)
                 acc = torch.cat((acc, acc2, pck.reshape(-1).double()))
-            if rendered:                                           # before the interaction block, which is read from the end
+            if refined:                                            # before the interaction block, which is read from the end
+                rt = acc.numel()
+                acc = torch.cat((acc, acc5))
+            if rendered:
                 at = acc.numel()
                 acc = torch.cat((acc, acc4))
             if interaction:
@@ -699,6 +712,8 @@ class Trainer:
                 out.update(finish_interaction(acc[-12:]))
             if rendered:
                 out.update(finish_rendered(acc[at:at + 8]))
+            if refined:
+                out.update(finish_refined(acc[rt:rt + REFINED_SUMS]))
             if json_path is not None:
                 rows = torch.cat(poses) if poses else torch.zeros((0, 128), dtype=torch.float64, device=dev)
                 if self.world > 1:                                 # ragged gather: pad every rank's block to the longest
@@ -933,6 +948,71 @@ def write_rendered_scores(path, ev):
     with open(path, 'a') as fo:
         fo.write('eval rendered \n')
         for k in RENDERED_KEYS:
+            if k in ev:
+                fo.write('%s: %.2f\n' % (k, ev[k]))
+
+
+REFINED_KEYS = ('ref_abs_left_joints', 'ref_abs_right_joints', 'ref_abs_left_verts', 'ref_abs_right_verts', 'ref_mpjpe_mm', 'ref_mpvpe_mm',
+                'cloud_res_mm', 'ref_cloud_res_mm', 'ref_inlier_share', 'refined_samples')
+REFINED_SUMS = 17
+REFINE_ITERS, REFINE_TRIM = 8, 0.03          # iterations and inlier distance (metres) of the evaluation's ICP
+
+
+def refined_sums(tup, batch, faces, rigid=False):
+    """test-mode 9-tuple, the batch (`cloud` [B, 2, P, 3] camera-space metres, `valid` [B, 2]) and the faces [2, Fc, 3] -> float64 [17] on the
+    device.  Each predicted absolute mesh is moved onto its hand's cloud (`F.mesh_icp`, REFINE_ITERS iterations, inliers within REFINE_TRIM; a
+    translation per iteration, or the Kabsch motion with `rigid`) and the hand's (R, t) is applied to its predicted absolute joints.  [0] the
+    number of samples; then, per quantity, the pair (left, right) of sums over the samples with that hand valid (valid == 1): [1:3] the mean
+    distance of the refined joints to the ground truth, [3:5] of the refined vertices, [5:7] the root mean square distance of the cloud's
+    inliers to the mesh before (an iters = 0 call) and [7:9] after, [9:11] the inliers after / the cloud's points with Z > 0 (0 without any),
+    [11:13] the number of such samples, [13:15] / [15:17] those of them with an inlier before / after (what the two residuals are means over)."""
+    vp, jp, vg, jg = tup[:4]
+    if 'cloud' not in batch:
+        raise KeyError("Trainer.evaluation: refined needs batch['cloud'], the hands' sensor points [B, 2, P, 3] in camera-space metres "
+                       "(F.depth2pcl, interhand.py H2O entries)")
+    cloud, valid = batch['cloud'], batch['valid']
+    _, _, _, rms0, in0 = F.mesh_icp(vp, faces, cloud, valid=valid, iters=0, trim=REFINE_TRIM)
+    vr, R, t, rms1, in1 = F.mesh_icp(vp, faces, cloud, valid=valid, iters=REFINE_ITERS, trim=REFINE_TRIM, rigid=rigid)
+    jr = torch.einsum('bhij,bhkj->bhki', R, jp.float()) + t[:, :, None]
+    has = valid == 1                                                                             # [B, 2]
+    live = (cloud[..., 2] > 0).sum(-1).double()
+    share = in1.double() / live.clamp(min=1)
+    ones = torch.ones_like(share)
+    terms = torch.stack((F.point_dist_sum(jr, jg).double() / jp.shape[-2], F.point_dist_sum(vr, vg).double() / vp.shape[-2], rms0.double(),
+                         rms1.double(), share, ones, (in0 > 0).double(), (in1 > 0).double()))   # [8, B, 2]
+    n = torch.full((1,), float(vp.shape[0]), dtype=torch.float64, device=vp.device)
+    return torch.cat((n, torch.where(has, terms, torch.zeros_like(terms)).sum(1).reshape(-1)))
+
+
+def finish_refined(acc):
+    """The accumulator of `refined_sums` -> 'ref_abs_left_joints' ... 'ref_abs_right_verts' in mm (the absolute errors after the refinement, means
+    over the samples with that hand valid; `abs_*` are means over all samples), 'ref_mpjpe_mm' / 'ref_mpvpe_mm' (mean of the two hands, or the
+    one there is), 'cloud_res_mm' / 'ref_cloud_res_mm' (root mean square inlier distance of the cloud to the mesh before / after, mean over the
+    hands with an inlier), 'ref_inlier_share' (inliers after / usable points, mean over the valid hands), 'refined_samples'.  A mean over
+    nothing is 0; without a sample only 'refined_samples'."""
+    a = [float(x) for x in acc]
+    out = {'refined_samples': int(round(a[0]))}
+    if out['refined_samples'] == 0:
+        return out
+    mean = lambda total, count: total / count if round(count) > 0 else 0.0
+    res = {}
+    for i, what in ((1, 'joints'), (3, 'verts')):
+        for h, hand in enumerate(('left', 'right')):
+            res['ref_abs_%s_%s' % (hand, what)] = mean(a[i + h], a[11 + h]) * 1000
+        there = [res['ref_abs_%s_%s' % (hand, what)] for h, hand in enumerate(('left', 'right')) if round(a[11 + h]) > 0]
+        res['ref_mpjpe_mm' if what == 'joints' else 'ref_mpvpe_mm'] = sum(there) / len(there) if there else 0.0
+    res['cloud_res_mm'] = mean(a[5] + a[6], a[13] + a[14]) * 1000
+    res['ref_cloud_res_mm'] = mean(a[7] + a[8], a[15] + a[16]) * 1000
+    res['ref_inlier_share'] = mean(a[9] + a[10], a[11] + a[12])
+    res.update(out)
+    return {k: res[k] for k in REFINED_KEYS}
+
+
+def write_refined_scores(path, ev):
+    """Append the figures of `evaluation(refined=...)` that are there as a block of their own (`key: %.2f`, like `write_rendered_scores`)."""
+    with open(path, 'a') as fo:
+        fo.write('eval refined \n')
+        for k in REFINED_KEYS:
             if k in ev:
                 fo.write('%s: %.2f\n' % (k, ev[k]))
 
