@@ -458,6 +458,26 @@ int pdf_mesh_penetration(const float* verts, const long long* faces, int B, int 
  * no scratch memory: two runs are bit-identical and a row's result does not depend on the other rows of the batch. */
 int pdf_mesh_icp(const float* verts, const long long* faces, const float* cloud, const float* valid, int B, int n, int Fc, int P, int iters,
                  float trim, int rigid, float* out_verts, float* R, float* t, float* rms, int* inliers, float* closest, int* tri, void* stream);
+/* Differentiable cloud-to-mesh loss.  Row (b, h): the mean squared distance from hand h's sensor points to the mesh of hand h of sample b, and
+ * its gradient with respect to that mesh's vertices.
+ * verts, faces, cloud, valid and trim have exactly the meaning they have for pdf_mesh_icp, and the association is that of pdf_mesh_icp with
+ * iters = 0, made by the same device code: a point with Z <= 0 is ignored; only the triangles that face the camera at the origin are
+ * candidates; q by the seven regions in the same order; the lowest face index wins a tie; p is an inlier when |p - q| < trim, strictly.
+ *   loss    [B,2] f32: (1/m) sum over the inliers of |p - q|^2, in m^2, m = the number of inliers; summed in double in a fixed order; 0 when m = 0
+ *   inliers [B,2] int32: m
+ *   grad    [B,2,n,3] f32 or NULL: d loss[b,h] / d verts[b,h].  With q = w_a a + w_b b + w_c c the envelope theorem gives
+ *           d |p - q|^2 / d a = -2 w_a (p - q), likewise for b and c, in the face, edge and vertex regions alike: for every inlier, corner k of
+ *           its triangle receives -(2/m) w_k (p - q).  m and the association are held constant (they are piecewise constant).  A vertex that no
+ *           inlier touches gets exactly 0.  The contributions to a vertex are added in ascending point order, in double.
+ *   tri     [B,2,P] int32 or NULL and closest [B,2,P,3] f32 or NULL: as pdf_mesh_icp's
+ *   bary    [B,2,P,3] f32 or NULL: (w_a, w_b, w_c), the corners in the face's own order: exactly one-hot in a vertex region, exactly 0 for the
+ *           opposite corner in an edge region, every weight in [0, 1]; (0, 0, 0) where tri = -1
+ * A hand with valid = 0 or without a point that is not ignored gives loss = 0, inliers = 0, grad = 0, tri = -1, closest = 0, bary = 0.
+ * 1 <= n <= 1024, 1 <= Fc <= 2048, 1 <= P <= 1024, trim > 0 and finite, verts, faces, cloud, loss and inliers not NULL, else PDF_E_BADARG with
+ * nothing launched; B <= 0 returns 0.  Finite input gives finite output.  One launch, one workgroup per row, no atomics, no scratch memory: two
+ * runs are bit-identical and a row's result does not depend on the other rows of the batch. */
+int pdf_cloud_mesh_loss(const float* verts, const long long* faces, const float* cloud, const float* valid, int B, int n, int Fc, int P, float trim,
+                        float* loss, int* inliers, float* grad, int* tri, float* closest, float* bary, void* stream);
 
 /* ---- hand renderer (csrc/render.hip) ------------------------------------------------------------ */
 /* Forward-only z-buffered rasteriser of both hands of every sample under that sample's pinhole camera (the reference's pytorch3d

@@ -15,6 +15,7 @@
 //   rewrites its vertex of the LDS copy as fp32(R v0 + t) from the ORIGINAL vertex it holds in registers, so rounding does not pile up over
 //   the iterations and out_verts is exactly the fp32 rounding of R v + t.
 // No atomics, no global scratch: two runs are bit-identical and a row does not depend on the other rows of the batch.
+// The same association feeds cloud_mesh_loss_kernel at the end of this file: the residual as a loss, with its gradient (pdf_cloud_mesh_loss).
 #include "common.h"
 #include "svd3.h"
 
@@ -32,6 +33,25 @@
 __device__ __forceinline__ float icp_det2(float p, float q, float r, float s) {
 #pragma clang fp contract(off)
     return p * q - r * s;
+}
+
+// The association is written with its fused multiply-adds spelled out and contraction off, so that every kernel that inlines it rounds alike
+// whatever the compiler makes of the code around it: with contraction left to the compiler two kernels chose different operands to fuse,
+// and a near-tie between two triangles then fell to different sides.  The forms are the ones mesh_icp_kernel has always run.
+// x0 x1 + y0 y1 + z0 z1 as fma(y0, y1, x0 x1) + z0 z1: the facing test
+__device__ __forceinline__ float icp_dot3(float x0, float x1, float y0, float y1, float z0, float z1) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(y0, y1, x0 * x1) + z0 * z1;
+}
+// u . v as fma(uz, vz, fma(ux, vx, uy vy)): the walk's d1 .. d6 and |q - p|^2
+__device__ __forceinline__ float icp_dot(float ux, float uy, float uz, float vx, float vy, float vz) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(uz, vz, __builtin_fmaf(ux, vx, uy * vy));
+}
+// v ab + w ac - ap as fma(ac, w, ab v) - ap: a coordinate of q - p
+__device__ __forceinline__ float icp_comb(float v, float ab, float w, float ac, float ap) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(ac, w, ab * v) - ap;
 }
 
 struct IcpShared {                                             // (the small members first: their addresses fit a DS instruction's 16-bit offset)
@@ -60,7 +80,7 @@ __device__ __forceinline__ int icp_facing(IcpShared& s, int Fc) {
             cx = s.vx[f.z]; cy = s.vy[f.z]; cz = s.vz[f.z];
             const float e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
             const float nx = icp_det2(e1y, e2z, e1z, e2y), ny = icp_det2(e1z, e2x, e1x, e2z), nz = icp_det2(e1x, e2y, e1y, e2x);
-            keep = nx * (ax + bx + cx) + ny * (ay + by + cy) + nz * (az + bz + cz) < 0.f;
+            keep = icp_dot3(nx, ax + bx + cx, ny, ay + by + cy, nz, az + bz + cz) < 0.f;
         }
         const unsigned long long mask = __ballot(keep);
         if (lane == 0) s.wave_n[wave] = __popcll(mask);
@@ -82,52 +102,63 @@ __device__ __forceinline__ int icp_facing(IcpShared& s, int Fc) {
     return total;
 }
 
-// closest point of the listed triangles to (px, py, pz): squared distance, the point and the face index (-1: the list is empty)
+// closest point of the listed triangles to (px, py, pz): squared distance, the point and the face index (-1: the list is empty).
+// BARY: also the weights (wa, wb, wc) of that triangle's corners in q = wa a + wb b + wc c: one-hot in a vertex region, the opposite corner's
+// exactly 0 in an edge region, all in [0, 1].  They are kept beside (v, w) and feed nothing that the distance is made of, so both
+// instantiations choose the same triangle and the same q.
+template <bool BARY>
 __device__ __forceinline__ void icp_walk(const IcpShared& s, int count, float px, float py, float pz, float& best, float& qx, float& qy, float& qz,
-                                         int& face) {
+                                         int& face, float& wa, float& wb, float& wc) {
     best = 3.0e38f; qx = qy = qz = 0.f; face = -1;
+    wa = wb = wc = 0.f;
     for (int j = 0; j < count; ++j) {
         const float4 a = s.ca[j], b = s.cb[j], c = s.cc[j];
         const float abx = b.x - a.x, aby = b.y - a.y, abz = b.z - a.z, acx = c.x - a.x, acy = c.y - a.y, acz = c.z - a.z;
         const float apx = px - a.x, apy = py - a.y, apz = pz - a.z;
         const float bpx = px - b.x, bpy = py - b.y, bpz = pz - b.z;
         const float cpx = px - c.x, cpy = py - c.y, cpz = pz - c.z;
-        const float d1 = abx * apx + aby * apy + abz * apz, d2 = acx * apx + acy * apy + acz * apz;
-        const float d3 = abx * bpx + aby * bpy + abz * bpz, d4 = acx * bpx + acy * bpy + acz * bpz;
-        const float d5 = abx * cpx + aby * cpy + abz * cpz, d6 = acx * cpx + acy * cpy + acz * cpz;
-        const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+        const float d1 = icp_dot(abx, aby, abz, apx, apy, apz), d2 = icp_dot(acx, acy, acz, apx, apy, apz);
+        const float d3 = icp_dot(abx, aby, abz, bpx, bpy, bpz), d4 = icp_dot(acx, acy, acz, bpx, bpy, bpz);
+        const float d5 = icp_dot(abx, aby, abz, cpx, cpy, cpz), d6 = icp_dot(acx, acy, acz, cpx, cpy, cpz);
+        const float vc = icp_det2(d1, d4, d3, d2), vb = icp_det2(d5, d2, d1, d6), va = icp_det2(d3, d6, d5, d4);
         // q = a + v ab + w ac; the face first, then the regions from the last of the order to the first, so the first that holds wins
         const float inv = __frcp_rn(fmaxf(va + vb + vc, ICP_TINY));
         float v = fminf(fmaxf(vb * inv, 0.f), 1.f), w = fminf(fmaxf(vc * inv, 0.f), 1.f);
+        bool near_a = true;                                    // a carries weight: false on edge BC and at the vertices B and C
         if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) {                                   // edge BC
             w = fminf((d4 - d3) * __frcp_rn(fmaxf((d4 - d3) + (d5 - d6), ICP_TINY)), 1.f);
             v = 1.f - w;
+            near_a = false;
         }
-        if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { v = 0.f; w = fminf(d2 * __frcp_rn(fmaxf(d2 - d6, ICP_TINY)), 1.f); }      // edge AC
-        if (d6 >= 0.f && d5 <= d6) { v = 0.f; w = 1.f; }                                       // vertex C
-        if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { v = fminf(d1 * __frcp_rn(fmaxf(d1 - d3, ICP_TINY)), 1.f); w = 0.f; }      // edge AB
-        if (d3 >= 0.f && d4 <= d3) { v = 1.f; w = 0.f; }                                       // vertex B
-        if (d1 <= 0.f && d2 <= 0.f) { v = 0.f; w = 0.f; }                                      // vertex A
-        const float rx = v * abx + w * acx - apx, ry = v * aby + w * acy - apy, rz = v * abz + w * acz - apz;      // q - p
-        const float dd = rx * rx + ry * ry + rz * rz;
-        if (dd < best) { best = dd; qx = px + rx; qy = py + ry; qz = pz + rz; face = __float_as_int(a.w); }
+        if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { v = 0.f; w = fminf(d2 * __frcp_rn(fmaxf(d2 - d6, ICP_TINY)), 1.f); near_a = true; }      // edge AC
+        if (d6 >= 0.f && d5 <= d6) { v = 0.f; w = 1.f; near_a = false; }                       // vertex C
+        if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { v = fminf(d1 * __frcp_rn(fmaxf(d1 - d3, ICP_TINY)), 1.f); w = 0.f; near_a = true; }      // edge AB
+        if (d3 >= 0.f && d4 <= d3) { v = 1.f; w = 0.f; near_a = false; }                       // vertex B
+        if (d1 <= 0.f && d2 <= 0.f) { v = 0.f; w = 0.f; near_a = true; }                       // vertex A
+        const float rx = icp_comb(v, abx, w, acx, apx), ry = icp_comb(v, aby, w, acy, apy), rz = icp_comb(v, abz, w, acz, apz);      // q - p
+        const float dd = icp_dot(rx, ry, rz, rx, ry, rz);
+        if (dd < best) {
+            best = dd; qx = px + rx; qy = py + ry; qz = pz + rz; face = __float_as_int(a.w);
+            if (BARY) { wa = near_a ? fmaxf(1.f - v - w, 0.f) : 0.f; wb = v; wc = w; }        // (1 - (1 - w) - w is not 0 for every w: hence near_a)
+        }
     }
 }
 
-// v[0..ICP_K) summed over the block in a fixed order -> out[0..ICP_K) in LDS (ends in a barrier): the xor butterfly per wave, then thread k
+// v[0..K) summed over the block in a fixed order -> out[0..K) in LDS (ends in a barrier): the xor butterfly per wave, then thread k
 // adds the 16 wave partials of sum k as a balanced tree
+template <int K>
 __device__ __forceinline__ void icp_block_sum(double* v, double* sm, double* out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < ICP_K; ++k) {
+    for (int k = 0; k < K; ++k) {
         const double r = wave_sum_d(v[k]);
-        if (lane == 0) sm[wave * ICP_K + k] = r;
+        if (lane == 0) sm[wave * K + k] = r;
     }
     __syncthreads();
-    if (threadIdx.x < ICP_K) {
+    if (threadIdx.x < K) {
         double p[ICP_W];
 #pragma unroll
-        for (int w = 0; w < ICP_W; ++w) p[w] = sm[w * ICP_K + threadIdx.x];
+        for (int w = 0; w < ICP_W; ++w) p[w] = sm[w * K + threadIdx.x];
 #pragma unroll
         for (int m = ICP_W / 2; m > 0; m /= 2) {
 #pragma unroll
@@ -216,13 +247,13 @@ __global__ __launch_bounds__(ICP_T) void mesh_icp_kernel(const float* __restrict
     if (t == 0) s.stop = 0;
     __syncthreads();
 
-    float best, qx, qy, qz;
+    float best, qx, qy, qz, wa, wb, wc;                        // (the weights are not computed here)
     int face;
     for (int it = 0; ; ++it) {
         const int count = icp_facing(s, Fc);                   // (ends in a barrier)
         const float px = pp[0], py = pp[1], pz = pp[2];
         best = 3.0e38f; qx = qy = qz = 0.f; face = -1;
-        if (__ballot(live) != 0ULL) icp_walk(s, count, px, py, pz, best, qx, qy, qz, face);      // wave-uniform; a dead lane's result is not used
+        if (__ballot(live) != 0ULL) icp_walk<false>(s, count, px, py, pz, best, qx, qy, qz, face, wa, wb, wc);      // wave-uniform; a dead lane's result is not used
         const bool in = live && face >= 0 && sqrtf(best) < trim;
         const double dpx = in ? px : 0.f, dpy = in ? py : 0.f, dpz = in ? pz : 0.f, dqx = in ? qx : 0.f, dqy = in ? qy : 0.f, dqz = in ? qz : 0.f;
         double a[ICP_K];
@@ -230,7 +261,7 @@ __global__ __launch_bounds__(ICP_T) void mesh_icp_kernel(const float* __restrict
         a[7] = dqx * dpx; a[8] = dqx * dpy; a[9] = dqx * dpz; a[10] = dqy * dpx; a[11] = dqy * dpy; a[12] = dqy * dpz;
         a[13] = dqz * dpx; a[14] = dqz * dpy; a[15] = dqz * dpz;
         a[16] = in ? (double)best : 0.0;
-        icp_block_sum(a, s.red, s.sum);
+        icp_block_sum<ICP_K>(a, s.red, s.sum);
         if (it == iters) break;                                // the final association: s.sum feeds rms and inliers
         if (t == 0 && !icp_step(s.sum, rigid, s.xf, s.svd)) s.stop = 1;
         __syncthreads();
@@ -269,6 +300,103 @@ PDF_API int pdf_mesh_icp(const float* verts, const long long* faces, const float
         return PDF_E_BADARG;
     hipLaunchKernelGGL(mesh_icp_kernel, dim3(2 * B), dim3(ICP_T), 0, s, verts, faces, cloud, valid, n, Fc, P, iters, trim, rigid, out_verts, R, t,
                        rms, inliers, closest, tri);
+    PDF_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- differentiable cloud-to-mesh loss (contract: pdf_cloud_mesh_loss in pdfnet_hip.h) ----------------------------------------------------
+// The association of mesh_icp_kernel with iters = 0 -- icp_facing and icp_walk, shared -- then loss = mean |p - q|^2 over the inliers and its
+// gradient with respect to the vertices: corner k of an inlier's triangle receives -(2/m) w_k (p - q) (the envelope theorem: q is the minimiser
+// over the triangle, so only the explicit dependence of q = wa a + wb b + wc c on the corners counts).
+// Gather without atomics: once the walk is over the corner list is dead, and behind the block sum's barriers lane t writes point t's record
+// over its head: s.ca[t] = (wa, wb, wc, corner indices 0 and 1 as 16-bit halves), s.cb[t] = (-(2/m) (p - q), corner index 2); a point that is
+// no inlier writes the index 0xffff, which is no vertex.  Lane t < n then reads the P records front to back, every lane the same record (two
+// broadcast 16-byte reads), and adds those that name vertex t, in double, in ascending point order.
+__global__ __launch_bounds__(ICP_T) void cloud_mesh_loss_kernel(const float* __restrict__ verts, const long long* __restrict__ faces,
+                                                                const float* __restrict__ cloud, const float* __restrict__ valid, int n, int Fc,
+                                                                int P, float trim, float* __restrict__ loss, int* __restrict__ inliers,
+                                                                float* __restrict__ grad, int* __restrict__ tri, float* __restrict__ closest,
+                                                                float* __restrict__ bary) {
+    __shared__ IcpShared s;
+    const int t = threadIdx.x;
+    const long row = blockIdx.x;
+    const int h = (int)(row & 1);
+    const float* pp = cloud + (row * P + min(t, P - 1)) * 3;
+    const float* vp = verts + (row * n + min(t, n - 1)) * 3;
+    const bool live = t < P && pp[2] > 0.f;
+    const bool row_ok = valid == nullptr || valid[row] != 0.f;
+    if (!__syncthreads_or(live && row_ok)) {                   // block-uniform: nothing to compare the hand with
+        if (t == 0) { loss[row] = 0.f; inliers[row] = 0; }
+        if (t < n && grad != nullptr) { float* g = grad + (row * n + t) * 3; g[0] = g[1] = g[2] = 0.f; }
+        if (t < P) {
+            if (closest != nullptr) { float* c = closest + (row * P + t) * 3; c[0] = c[1] = c[2] = 0.f; }
+            if (bary != nullptr) { float* w = bary + (row * P + t) * 3; w[0] = w[1] = w[2] = 0.f; }
+            if (tri != nullptr) tri[row * P + t] = -1;
+        }
+        return;
+    }
+    if (t < n) { s.vx[t] = vp[0]; s.vy[t] = vp[1]; s.vz[t] = vp[2]; }
+    const long long* fo = faces + (long)h * Fc * 3;
+    for (int g = t; g < Fc; g += ICP_T) {
+        ushort4 f;                                             // an index outside [0, n) is clamped: it must not leave the staged planes
+        f.x = (unsigned short)min(max(fo[3 * g + 0], 0LL), (long long)(n - 1));
+        f.y = (unsigned short)min(max(fo[3 * g + 1], 0LL), (long long)(n - 1));
+        f.z = (unsigned short)min(max(fo[3 * g + 2], 0LL), (long long)(n - 1));
+        f.w = 0;
+        s.tri[g] = f;
+    }
+    __syncthreads();
+
+    const int count = icp_facing(s, Fc);                       // (ends in a barrier)
+    const float px = pp[0], py = pp[1], pz = pp[2];
+    float best = 3.0e38f, qx = 0.f, qy = 0.f, qz = 0.f, wa = 0.f, wb = 0.f, wc = 0.f;
+    int face = -1;
+    if (__ballot(live) != 0ULL) icp_walk<true>(s, count, px, py, pz, best, qx, qy, qz, face, wa, wb, wc);      // wave-uniform
+    const bool hit = live && face >= 0, in = hit && sqrtf(best) < trim;
+    double a[2] = {in ? 1.0 : 0.0, in ? (double)best : 0.0};
+    icp_block_sum<2>(a, s.red, s.sum);                         // (its barriers: every lane has left the walk, the corner list is dead)
+    const double m = s.sum[0];
+    if (t == 0) {
+        loss[row] = m > 0.0 ? (float)(s.sum[1] / m) : 0.f;
+        inliers[row] = (int)m;
+    }
+    if (t < P) {
+        if (closest != nullptr) { float* c = closest + (row * P + t) * 3; c[0] = hit ? qx : 0.f; c[1] = hit ? qy : 0.f; c[2] = hit ? qz : 0.f; }
+        if (bary != nullptr) { float* w = bary + (row * P + t) * 3; w[0] = hit ? wa : 0.f; w[1] = hit ? wb : 0.f; w[2] = hit ? wc : 0.f; }
+        if (tri != nullptr) tri[row * P + t] = hit ? face : -1;
+    }
+    if (grad == nullptr) return;                               // block-uniform
+    if (t < P) {
+        const float sc = in ? (float)(-2.0 / m) : 0.f;
+        ushort4 f = make_ushort4(0xffff, 0xffff, 0xffff, 0);
+        if (in) f = s.tri[face];                               // face < Fc: it came out of the list
+        s.ca[t] = make_float4(wa, wb, wc, __int_as_float((int)f.x | ((int)f.y << 16)));
+        s.cb[t] = make_float4(in ? sc * (px - qx) : 0.f, in ? sc * (py - qy) : 0.f, in ? sc * (pz - qz) : 0.f, __int_as_float((int)f.z));
+    }
+    __syncthreads();
+    if (t < n) {
+        double gx = 0.0, gy = 0.0, gz = 0.0;
+        for (int j = 0; j < P; ++j) {
+            const float4 ra = s.ca[j], rb = s.cb[j];
+            const int i01 = __float_as_int(ra.w), i2 = __float_as_int(rb.w);
+            if ((i01 & 0xffff) == t) { gx += (double)(ra.x * rb.x); gy += (double)(ra.x * rb.y); gz += (double)(ra.x * rb.z); }
+            if (((i01 >> 16) & 0xffff) == t) { gx += (double)(ra.y * rb.x); gy += (double)(ra.y * rb.y); gz += (double)(ra.y * rb.z); }
+            if (i2 == t) { gx += (double)(ra.z * rb.x); gy += (double)(ra.z * rb.y); gz += (double)(ra.z * rb.z); }
+        }
+        float* g = grad + (row * n + t) * 3;
+        g[0] = (float)gx; g[1] = (float)gy; g[2] = (float)gz;
+    }
+}
+
+PDF_API int pdf_cloud_mesh_loss(const float* verts, const long long* faces, const float* cloud, const float* valid, int B, int n, int Fc, int P,
+                                float trim, float* loss, int* inliers, float* grad, int* tri, float* closest, float* bary, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (n < 1 || n > ICP_MAXN || Fc < 1 || Fc > ICP_MAXF || P < 1 || P > ICP_MAXP || !(trim > 0.f) || !(trim <= 3.0e38f) || verts == nullptr ||
+        faces == nullptr || cloud == nullptr || loss == nullptr || inliers == nullptr)
+        return PDF_E_BADARG;
+    hipLaunchKernelGGL(cloud_mesh_loss_kernel, dim3(2 * B), dim3(ICP_T), 0, s, verts, faces, cloud, valid, n, Fc, P, trim, loss, inliers, grad, tri,
+                       closest, bary);
     PDF_LAUNCH_CHECK();
     return 0;
 }

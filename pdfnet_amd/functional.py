@@ -2450,6 +2450,29 @@ def mesh_penetration(verts, faces, return_fields=False):
     return (count, depth, gap, wind, dist) if return_fields else (count, depth, gap)
 
 
+def _cloud_args(name, verts, faces, cloud, valid, trim):
+    """The checks `mesh_icp` and `cloud_mesh_loss` share -> (verts, faces, cloud, valid or None as detached contiguous f32 / int64 tensors,
+    lead, n, Fc, P, trim)."""
+    hip.require_gpu(verts, faces, cloud, valid)
+    v, f, c = verts.detach().float().contiguous(), faces.detach().long().contiguous(), cloud.detach().float().contiguous()
+    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
+        raise ValueError("pdfnet_amd: %s wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (name, tuple(v.shape), tuple(f.shape)))
+    lead, n, Fc = v.shape[:-2], v.shape[-2], f.shape[1]
+    if c.dim() != v.dim() or c.shape[:-2] != lead or c.shape[-1] != 3:
+        raise ValueError("pdfnet_amd: %s wants cloud %s for verts %s, got %s" % (name, tuple(lead) + ('P', 3), tuple(v.shape), tuple(c.shape)))
+    P, trim = c.shape[-2], float(trim)
+    if not (1 <= n <= 1024 and 1 <= Fc <= 2048 and 1 <= P <= 1024):
+        raise ValueError("pdfnet_amd: %s takes 1 to 1024 vertices, 1 to 2048 faces and 1 to 1024 points per hand, got %d, %d and %d" % (name, n, Fc, P))
+    if not 0.0 < trim < float('inf'):
+        raise ValueError("pdfnet_amd: %s takes a finite trim > 0, got %r" % (name, trim))
+    va = None
+    if valid is not None:
+        va = valid.detach().float().contiguous()
+        if va.shape != lead:
+            raise ValueError("pdfnet_amd: %s wants valid %s, got %s" % (name, tuple(lead), tuple(va.shape)))
+    return v, f, c, va, lead, n, Fc, P, trim
+
+
 def mesh_icp(verts, faces, cloud, valid=None, iters=8, trim=0.03, rigid=False, return_fields=False):
     """verts [..., 2, n, 3] camera-space metres (left, right hand), faces [2, Fc, 3] int64 (the loss module's `faces_pair`, oriented outwards),
     cloud [..., 2, P, 3] that hand's sensor points in camera-space metres (`depth2pcl`'s; a point with Z <= 0 is ignored), valid [..., 2] or
@@ -2460,23 +2483,10 @@ def mesh_icp(verts, faces, cloud, valid=None, iters=8, trim=0.03, rigid=False, r
     return_fields: also (closest [..., 2, P, 3], tri int32 [..., 2, P]), each point's closest surface point and its face, (0, 0, 0) and -1
     where there is none.  A hand with valid = 0 or without a usable point comes back unchanged with R = I, t = 0, rms = 0, inliers = 0.
     The contract is `pdf_mesh_icp`'s in pdfnet_hip.h.  n, P <= 1024, Fc <= 2048, iters <= 64.  No gradient; deterministic."""
-    hip.require_gpu(verts, faces, cloud, valid)
-    v, f, c = verts.detach().float().contiguous(), faces.detach().long().contiguous(), cloud.detach().float().contiguous()
-    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
-        raise ValueError("pdfnet_amd: mesh_icp wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
-    lead, n, Fc = v.shape[:-2], v.shape[-2], f.shape[1]
-    if c.dim() != v.dim() or c.shape[:-2] != lead or c.shape[-1] != 3:
-        raise ValueError("pdfnet_amd: mesh_icp wants cloud %s for verts %s, got %s" % (tuple(lead) + ('P', 3), tuple(v.shape), tuple(c.shape)))
-    P, iters, trim = c.shape[-2], int(iters), float(trim)
-    if not (1 <= n <= 1024 and 1 <= Fc <= 2048 and 1 <= P <= 1024):
-        raise ValueError("pdfnet_amd: mesh_icp takes 1 to 1024 vertices, 1 to 2048 faces and 1 to 1024 points per hand, got %d, %d and %d" % (n, Fc, P))
-    if not (0 <= iters <= 64 and 0.0 < trim < float('inf')):
-        raise ValueError("pdfnet_amd: mesh_icp takes 0 to 64 iterations and a finite trim > 0, got %r and %r" % (iters, trim))
-    va = None
-    if valid is not None:
-        va = valid.detach().float().contiguous()
-        if va.shape != lead:
-            raise ValueError("pdfnet_amd: mesh_icp wants valid %s, got %s" % (tuple(lead), tuple(va.shape)))
+    v, f, c, va, lead, n, Fc, P, trim = _cloud_args('mesh_icp', verts, faces, cloud, valid, trim)
+    iters = int(iters)
+    if not 0 <= iters <= 64:
+        raise ValueError("pdfnet_amd: mesh_icp takes 0 to 64 iterations, got %r" % (iters,))
     dev = v.device
     out, R, t = torch.empty_like(v), torch.empty(lead + (3, 3), dtype=torch.float32, device=dev), torch.empty(lead + (3,), dtype=torch.float32, device=dev)
     rms, inliers = torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev)
@@ -2485,6 +2495,42 @@ def mesh_icp(verts, faces, cloud, valid=None, iters=8, trim=0.03, rigid=False, r
     _L().pdf_mesh_icp(ptr(v), ptr(f), ptr(c), ptr(va), rms.numel() // 2, n, Fc, P, iters, trim, int(bool(rigid)), ptr(out), ptr(R), ptr(t), ptr(rms),
                       ptr(inliers), ptr(closest), ptr(tri), stream())
     return (out, R, t, rms, inliers, closest, tri) if return_fields else (out, R, t, rms, inliers)
+
+
+class _CloudMeshLoss(torch.autograd.Function):
+    """loss [..., 2] of `cloud_mesh_loss`; the kernel writes d loss / d verts in the forward launch when verts needs it."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, cloud, valid, trim, fields, want_grad):
+        v, f, c, va, lead, n, Fc, P, trim = _cloud_args('cloud_mesh_loss', verts, faces, cloud, valid, trim)
+        dev = v.device
+        loss, inliers = torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev)
+        grad = torch.empty_like(v) if want_grad else None
+        tri = torch.empty(lead + (P,), dtype=torch.int32, device=dev) if fields else None
+        bary, closest = (torch.empty_like(c), torch.empty_like(c)) if fields else (None, None)
+        _L().pdf_cloud_mesh_loss(ptr(v), ptr(f), ptr(c), ptr(va), loss.numel() // 2, n, Fc, P, trim, ptr(loss), ptr(inliers), ptr(grad), ptr(tri),
+                                 ptr(closest), ptr(bary), stream())
+        ctx.grad, ctx.dtype = grad, verts.dtype
+        extra = (inliers, tri, bary, closest) if fields else (inliers,)
+        ctx.mark_non_differentiable(*extra)
+        return (loss,) + extra
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *unused):
+        return (g[..., None, None] * ctx.grad).to(ctx.dtype), None, None, None, None, None, None
+
+
+def cloud_mesh_loss(verts, faces, cloud, valid=None, trim=0.03, return_fields=False):
+    """verts [..., 2, n, 3], faces [2, Fc, 3], cloud [..., 2, P, 3], valid [..., 2] or None as `mesh_icp` takes them -> loss [..., 2] in m^2: per
+    hand the mean of |p - q|^2 over the cloud points p closer than `trim` to the camera-facing surface of that hand's mesh, q their closest
+    surface points (the association of `mesh_icp(iters=0)`, by the same device code); 0 without such a point or with valid = 0.
+    Differentiable once, with respect to `verts` only: corner k of a point's triangle receives -(2/m) w_k (p - q), with the association and the
+    number m of inliers held constant.  The gradient comes out of the forward launch; backward is one multiplication.
+    return_fields: (loss, inliers int32 [..., 2], tri int32 [..., 2, P], bary [..., 2, P, 3], closest [..., 2, P, 3]).
+    The contract is `pdf_cloud_mesh_loss`'s in pdfnet_hip.h.  n, P <= 1024, Fc <= 2048.  Deterministic."""
+    out = _CloudMeshLoss.apply(verts, faces, cloud, valid, trim, bool(return_fields), torch.is_grad_enabled() and verts.requires_grad)
+    return out if return_fields else out[0]
 
 
 # ----------------------------------------------------------------------------------------------

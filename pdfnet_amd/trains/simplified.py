@@ -73,11 +73,28 @@ def projection_batch(scale, trans2d, pts, img_size):
     return s * pts[..., :2] + t
 
 
+def cloud_term(vp, root, ind, batch, faces, input_res, down_ratio=4, trim=0.03):
+    """The cloud-to-mesh training term -> [B] in mm^2: sum over the valid hands of `F.cloud_mesh_loss` (the mean squared distance from the hand's
+    sensor points within `trim` metres to the camera-facing surface of its predicted mesh), times 1e6.
+    vp [2, B, 778, 3] root-relative predicted vertices and root [2, B, 3] the predicted root parameters, both (left, right) as the mesh terms
+    take them; the absolute vertices are vp + uv_root_3d(...) with the batch's `ind`, as in abs_verts_loss.  batch: `cloud` [B, 2, P, 3]
+    camera-space metres, `valid` [B, 2], `K_new`; faces [2, Fc, 3].  Needs no annotation; differentiable in vp and root."""
+    if 'cloud' not in batch:
+        raise KeyError("CtdetLoss: cloud_weight > 0 needs batch['cloud'], the hands' sensor points [B, 2, P, 3] in camera-space metres "
+                       "(F.depth2pcl, interhand.py H2O entries)")
+    valid = batch['valid']
+    root_pred = uv_root_3d(ind.t(), root[..., 1:] / 100, 0.4 + root[..., 0] / 100, batch['K_new'], input_res, down_ratio)
+    verts = (vp + root_pred).transpose(0, 1).contiguous()                                                   # [B, 2, 778, 3]
+    return 1e6 * (valid * F.cloud_mesh_loss(verts, faces, batch['cloud'], valid=valid, trim=trim)).sum(1)
+
+
 FORK_DENSE_LOSS = os.environ.get("PDFNET_FORK_DENSE_LOSS", "1") != "0"
 
 
 class CtdetLoss(nn.Module):
-    """opt fields used: size_train, center_weight (200), reproj_weight (1), bone_dir_weight (200), down_ratio (4).
+    """opt fields used: size_train, center_weight (200), reproj_weight (1), bone_dir_weight (200), down_ratio (4), cloud_weight (0: the
+    cloud-to-mesh term `cloud_term` is neither computed nor launched; > 0: train mode adds cloud_weight * cloud_loss and reports
+    stats['cloud_loss']), cloud_trim (0.03 m).
     `consts`: {'full_regressor_left/right' [21,778], 'faces_left/right' [1538,3] int64}."""
 
     def __init__(self, opt, consts):
@@ -112,8 +129,16 @@ class CtdetLoss(nn.Module):
             loss = mp + self.dense_part(t)
             stats = {k: t[k] for k in self._ORDER}
             stats['loss'] = loss
-            return loss, stats, None, None
-        return self.total(t, epoch)
+        else:
+            loss, stats = self.total(t, epoch)[:2]
+        cw = getattr(self.opt, 'cloud_weight', 0)
+        if cw > 0:                                           # the self-supervised term: the predicted mesh against the measured depth
+            cl = cloud_term(_pair(result['verts3d']), _pair(paramsDict['root']), ind, batch, self.faces_pair, int(self.opt.size_train[0]),
+                            getattr(self.opt, 'down_ratio', 4), getattr(self.opt, 'cloud_trim', 0.03))
+            loss = loss + cw * cl
+            stats['cloud_loss'] = cl
+            stats['loss'] = loss
+        return loss, stats, None, None
 
     def dense_terms(self, otherInfo, batch):
         """The terms on the encoder's dense maps: hand masks (:368), joint heat-maps (:374), centre heat-map (:376,391) --
