@@ -250,7 +250,7 @@ _x3d_cache = {}
 def set_x3(mode):
     """Which launches run as x3 products (include/pdfnet_hip.h pdf_set_x3_mode: bit 0 Winograd-domain products of the wide layers, bit 1 the
     transposed convolutions, bit 2 the fused mesh decoder's linear products; None = the environment's choice).  Drops the cached workspace sizes, which
-    depend on it."""
+    depend on it; recorded tapes (taped.py) compare the mode on every call and are dropped there."""
     _L().pdf_set_x3_mode(-1 if mode is None else int(mode))
     _wino_cache.clear()
     _wino_voff.clear()

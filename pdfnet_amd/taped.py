@@ -22,11 +22,26 @@ is the segment.  Same contract as torch.cuda.make_graphed_callables, restated fo
   * the few aten kernels inside the segment (gradient fan-in additions, zero fills) are taped as out-variant calls on the pinned tensors; any
     other aten kernel aborts the recording and the segment stays eager.
 Results are bit-identical to the eager segment (`tests/test_trainer_gpu.py::test_taped_trunk_equals_the_eager_trunk_bit_for_bit`,
-`::test_taped_trunk_inside_the_train_step`, `::test_taped_trunk_is_not_recorded_over_accumulated_gradients`).
+`::test_taped_trunk_inside_the_train_step`, `::test_taped_trunk_is_not_recorded_over_accumulated_gradients`;
+after every kind of change named under "What a tape depends on" below: `tests/test_taped_stale_gpu.py`).
 
 Guard rails (round 6): a recording is REFUSED -- the call runs eagerly and the next qualifying call tries again -- while any gradient of the
 segment's parameters is non-zero (the recording pass zeroes them afterwards: with a micro-batch already accumulated that would lose it);
 `TapedSegment.pinned_bytes()` reports what the tapes hold alive (bench.py: config.taped_pinned_mb).
+
+What a tape depends on: the arguments it replays hold raw device addresses, workspace sizes and offsets, option structures and scalar
+hyper-parameters, all read once by the recording pass.  A tape is FOUND by its key (input shape, dtype and stride, the bf16 GEMM and storage
+modes, the stream) and is VALID only while `tape_state` gives what it gave when the tape was recorded:
+  * the library's x3 mode (`functional.set_x3`: it moves the transformed input inside the Winograd workspace and resizes the workspace);
+  * the module switches the segment's Functions read per call (`SWITCHES`);
+  * per parameter of the segment's modules: the address of its data, the address of its gradient, `requires_grad` (a second Trainer on
+    the same model re-points all of them at its own flat buffers -- every FlatAdam also bumps `TRAINERS`, which is part of the state; a
+    frozen weight drops its weight-gradient launch);
+  * per BatchNorm: `momentum` and `eps` (floats inside the recorded arguments).
+Every qualifying call computes that state first.  When it differs from the one the segment saw last, every entry is dropped (its pinned
+tensors are freed unless a pending backward still holds them), the parameters are checked again for Trainer ownership, and the call records
+anew -- or runs eagerly while the gradients are not clean, or the parameters are not a Trainer's.  What the kernels read THROUGH those
+addresses may change freely: weights updated or loaded in place, running statistics, the input.
 """
 import os
 
@@ -39,6 +54,10 @@ from . import hip
 
 TRUNK_TAPE = os.environ.get("PDFNET_TRUNK_TAPE", "1") != "0"
 SUSPEND = False                                                  # bench's instrumented step: per-launch timers wrap the Python entry points
+
+# module switches of `functional` that the segment's Functions read on every call: a tape holds what they were when it was recorded
+SWITCHES = ('WINOGRAD', 'WINOGRAD_KEEP_V', 'WINOGRAD_SHARE', 'BN_EPILOGUE_STATS', 'BN_EPILOGUE_STATS_BF16', 'ASYNC_WGRAD_MIN_FLOP',
+            'BF16_SHADOWS', 'TRANSPOSED_SHADOWS')
 
 _ALLOC = ('empty', 'empty_like', 'empty_strided', 'new_empty', 'record_stream')
 _VIEW = ('view', 'reshape', '_unsafe_view', 'permute', 'transpose', 'expand', 'slice', 'select', 'squeeze', 'unsqueeze', 't.', 'alias', 'detach',
@@ -110,6 +129,27 @@ class _Replay(Function):
         return None, None, e['gx'].detach()
 
 
+def _x3_mode():
+    return F._L().pdf_debug_x3_mode()
+
+
+TRAINERS = 0                                                     # bumped by every FlatAdam: it re-points the parameters it adopts
+
+
+def new_trainer():
+    global TRAINERS
+    TRAINERS += 1
+
+
+def tape_state(params, batchnorms):
+    """Everything a tape bakes into its arguments beyond its key (module docstring): equal states <=> a recorded tape may be replayed.
+    params: the parameters of the segment's modules; batchnorms: its BatchNorm modules."""
+    grads = [p.grad for p in params]
+    return (_x3_mode(), TRAINERS, tuple([getattr(F, s) for s in SWITCHES]), tuple([p.data_ptr() for p in params]),
+            tuple([0 if g is None else g.data_ptr() for g in grads]), tuple([p.requires_grad for p in params]),
+            tuple([(b.momentum, b.eps) for b in batchnorms]))
+
+
 class TapedSegment:
     """stages: functions f_k with outs_k = f_k(outs_{k-1}) (outs_0 = f_0(x)), each a fixed chain of this library's Functions over
     modules[k] (whose parameters must all be Trainer-owned).  `segment(x)` -> (outs_0, .., outs_n) from tape replays; anything that
@@ -123,7 +163,9 @@ class TapedSegment:
         self.entries = {}
         self.enabled = TRUNK_TAPE
         self._bns = None
+        self._params = None
         self._params_ok = False
+        self._state = None                                     # tape_state() of the last qualifying call: what every entry was recorded under
 
     def eager(self, x):
         outs = []
@@ -141,12 +183,26 @@ class TapedSegment:
             return False
         if not all(b.training for b in self._batchnorms()):    # a frozen BatchNorm inside a train-mode stage (layers.freeze_batchnorm): eager
             return False
-        if not self._params_ok:                                # (checked until it holds once: the Trainer tags its parameters for good)
-            for m in self.modules:
-                for p in m.parameters():
-                    if p.requires_grad and (not getattr(p, '_pdf_main_grad', False) or p.grad is None):
-                        return False
-            self._params_ok = True
+        return self._revalidate()
+
+    def _revalidate(self):
+        """Drops every tape once anything it baked in has changed (module docstring) -> whether the segment's parameters are a Trainer's.
+        Entries exist only while `_params_ok` holds and `_state` is what they were recorded under."""
+        if self._params_ok:
+            if tape_state(self._params, self._batchnorms()) == self._state:
+                return True
+            self.entries.clear()                               # (a pending backward keeps its own entry alive through its ctx)
+            self._params_ok = False
+        # (walked until it holds, and again after every change: whoever replaces a module or a parameter needs a new trainer for it)
+        params = []
+        for m in self.modules:
+            for p in m.parameters():
+                if p.requires_grad and (not getattr(p, '_pdf_main_grad', False) or p.grad is None):
+                    return False
+                params.append(p)
+        self._params, self._bns = params, None
+        self._state = tape_state(params, self._batchnorms())
+        self._params_ok = True
         return True
 
     def _batchnorms(self):
@@ -230,11 +286,14 @@ class TapedSegment:
             import warnings
             warnings.warn("pdfnet_amd: segment not taped, it runs aten kernels the tape does not know: %s" % sorted(set(rec.refused)))
             return False
-        return {'busy': False, 'x': sx, 'outs': tuple(outs), 'gouts': gouts, 'gx': gin, 'fwd': fwd, 'bwd': bwd, 'pins': pins, 'wg_keys': wg_keys,
-                'stream': hip._raw_stream(hip._raw_device()), 'pinned_bytes': _storage_bytes(pins)}
+        entry = {'busy': False, 'x': sx, 'outs': tuple(outs), 'gouts': gouts, 'gx': gin, 'fwd': fwd, 'bwd': bwd, 'pins': pins, 'wg_keys': wg_keys,
+                 'stream': hip._raw_stream(hip._raw_device())}
+        entry['pinned_bytes'] = _storage_bytes(entry)          # (the input, output and gradient buffers are held as long as the pins)
+        return entry
 
     def pinned_bytes(self):
-        """Device bytes the recorded tapes keep alive for the life of the process (every activation of every recorded signature)."""
+        """Device bytes the recorded tapes keep alive while they are valid (every activation of every recorded signature, and the buffers
+        the replay copies its input and output gradients into)."""
         return sum(e['pinned_bytes'] for e in self.entries.values() if e)
 
 

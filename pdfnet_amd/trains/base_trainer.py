@@ -18,6 +18,7 @@ import torch.distributed as dist
 
 from .. import functional as F
 from .. import hip
+from .. import taped
 
 
 class ModleWithLoss(torch.nn.Module):
@@ -82,6 +83,7 @@ class FlatAdam:
             p.grad = self.flat_g[o:o + k].as_strided(p.shape, p.stride())
             self._grad_views.append(p.grad)
             p._pdf_main_grad = True                   # HIP backward kernels accumulate straight into this view
+        taped.new_trainer()                            # tapes recorded over the previous buffers of these parameters are stale
         pos = {id(p): i for i, p in enumerate(self.params)}
         order = self.params if ckpt_order is None else [p for p in ckpt_order]
         assert len(order) == len(self.params) and all(id(p) in pos for p in order), "FlatAdam: ckpt_order must be a permutation of params"

@@ -330,15 +330,24 @@ def test_taped_trunk_is_not_recorded_over_accumulated_gradients(monkeypatch):
     from pdfnet_amd import functional as F
     from pdfnet_amd import taped
     from pdfnet_amd.trains.base_trainer import Trainer
-    monkeypatch.setattr(taped, 'TRUNK_TAPE', True)
     opt, m, crit, _ = _setup(R=128, B=2)
     tr = Trainer(opt, m, crit, lr=1e-4)
     m.train()
     enc = m.encoder
-    enc.__dict__.pop('_trunk_seg', None)
     x = torch.randn(4, 64, 32, 32, device='cuda').contiguous(memory_format=torch.channels_last)
-    tr.optimizer.zero_grad()
     w = enc.resnet.layer2[0].conv1.weight
+    monkeypatch.setattr(taped, 'TRUNK_TAPE', False)                # the clean eager gradient of this input
+    enc.__dict__.pop('_trunk_seg', None)
+    tr.optimizer.zero_grad()
+    outs = enc.trunk_layers(x.clone().requires_grad_())
+    torch.autograd.backward(outs, [torch.ones_like(o) for o in outs])
+    F.join_wgrad()
+    torch.cuda.synchronize()
+    g0 = w.grad.clone()
+    assert float(g0.abs().max()) > 0
+    monkeypatch.setattr(taped, 'TRUNK_TAPE', True)
+    enc.__dict__.pop('_trunk_seg', None)
+    tr.optimizer.zero_grad()
     w.grad.fill_(0.25)                                           # "a previous micro-batch"
     xr = x.clone().requires_grad_()
     outs = enc.trunk_layers(xr)
@@ -347,7 +356,7 @@ def test_taped_trunk_is_not_recorded_over_accumulated_gradients(monkeypatch):
     torch.autograd.backward(outs, [torch.ones_like(o) for o in outs])
     F.join_wgrad()
     torch.cuda.synchronize()
-    assert float((w.grad - 0.25).abs().max()) > 0 and float(w.grad.abs().min()) >= 0          # accumulated ON TOP of the 0.25, not from zero
+    assert torch.allclose(w.grad - 0.25, g0, rtol=1e-5, atol=1e-6)      # accumulated ON TOP of the 0.25, not from zero
     g1 = w.grad.clone()
     tr.optimizer.zero_grad()
     xr = x.clone().requires_grad_()
