@@ -478,6 +478,40 @@ int pdf_mesh_icp(const float* verts, const long long* faces, const float* cloud,
  * runs are bit-identical and a row's result does not depend on the other rows of the batch. */
 int pdf_cloud_mesh_loss(const float* verts, const long long* faces, const float* cloud, const float* valid, int B, int n, int Fc, int P, float trim,
                         float* loss, int* inliers, float* grad, int* tri, float* closest, float* bary, void* stream);
+/* Visibility-aware mesh-to-cloud loss (csrc/meshcloud.hip): the other direction.  Row (b, h): the mean squared distance from the vertices of
+ * hand h of sample b THAT THE CAMERA SEES to their nearest sensor points of hand h, and its gradient with respect to those vertices.
+ * verts, faces (both hands oriented outwards), cloud, valid and trim have exactly the meaning they have for pdf_mesh_icp; a cloud point with
+ * Z <= 0 is ignored.  All arithmetic is fp32 unless said otherwise.
+ *   Facing    a triangle of either hand faces the camera when n . (a + b + c) < 0, n = (b - a) x (c - a) from separately rounded products:
+ *             pdf_mesh_icp's rule, evaluated by the same forms.
+ *   Front     vertex i of hand h is front when it is a corner of at least one facing triangle of hand h.
+ *   Occluders of vertex i: the facing triangles of hand h that do not have index i as a corner, and, when valid[b,1-h] != 0 (NULL: valid),
+ *             all facing triangles of hand 1-h.
+ *   Occlusion by one occluder (a, b, c) of the vertex v: with a' = a - v, b' = b - v, c' = c - v,
+ *             s0 = v . (b' x c'), s1 = v . (c' x a'), s2 = v . (a' x b'), S = s0 + s1 + s2, det = a' . (b' x c').
+ *             The ray from the vertex to the camera at the origin meets the triangle when (s0, s1, s2 >= 0 and S > 0) or (s0, s1, s2 <= 0 and
+ *             S < 0): non-strict, so a ray through a shared edge or vertex is hit.  Each s_k is evaluated from the lower to the higher vertex
+ *             index of its edge and negated as needed (the cross products from separately rounded products, so this is the same bits as the
+ *             direct evaluation): the two faces at an edge agree and a closed surface has no gap.  With D = -det if S > 0, else det, and
+ *             A = |S|, the occluder hides the vertex when D < A and D |v| > margin A: the hit lies between camera and vertex, more than
+ *             `margin` metres from the vertex along the ray.  No division is involved.
+ *   Visible   valid[b,h] != 0 and front(i) and no occluder hides i.
+ *   Match     a visible vertex takes the cloud point of hand h with Z > 0 at the smallest squared distance; a strictly smaller value replaces
+ *             the best, so the lowest point index wins a tie.  It is an inlier when |v - p| < trim, strictly.
+ *   loss    [B,2] f32: (1/m) sum over the inliers of |v - p|^2, in m^2, m = the number of inliers; summed in double in ascending vertex order by
+ *           the fixed-order block reduction of pdf_mesh_icp; 0 when m = 0
+ *   inliers [B,2] int32: m;  visible [B,2] int32: the number of visible vertices
+ *   grad    [B,2,n,3] f32 or NULL: (2/m) (v - p) on an inlier vertex, exactly 0 elsewhere.  Visibility, the match and m are held constant (they
+ *           are piecewise constant).
+ *   vis     [B,2,n] int32 or NULL: 1 or 0
+ *   nn      [B,2,n] int32 or NULL: the matched point's index; -1 for a vertex that is not visible or when no cloud point is usable
+ * A hand with valid = 0: every output of the row is 0 and nn is -1.  Without a usable point visibility is computed as usual while loss, inliers
+ * and grad are 0 and nn is -1.
+ * 1 <= n <= 1024, 1 <= Fc <= 2048, 1 <= P <= 1024, trim > 0 and finite, margin >= 0 and finite, verts, faces, cloud, loss, inliers and visible
+ * not NULL, else PDF_E_BADARG with nothing launched; B <= 0 returns 0.  Finite input gives finite output.  One launch, one workgroup per row,
+ * no atomics, no scratch memory: two runs are bit-identical and a row depends only on the two hands of its own sample. */
+int pdf_mesh_cloud_loss(const float* verts, const long long* faces, const float* cloud, const float* valid, int B, int n, int Fc, int P, float trim,
+                        float margin, float* loss, int* inliers, int* visible, float* grad, int* vis, int* nn, void* stream);
 
 /* ---- hand renderer (csrc/render.hip) ------------------------------------------------------------ */
 /* Forward-only z-buffered rasteriser of both hands of every sample under that sample's pinhole camera (the reference's pytorch3d

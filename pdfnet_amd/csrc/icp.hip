@@ -18,36 +18,12 @@
 // The same association feeds cloud_mesh_loss_kernel at the end of this file: the residual as a loss, with its gradient (pdf_cloud_mesh_loss).
 #include "common.h"
 #include "svd3.h"
+#include "icp_common.h"                                         // ICP_T .. ICP_MAXP, icp_det2, icp_dot3, icp_dot, icp_block_sum (shared with meshcloud.hip)
 
-#define ICP_T 1024
-#define ICP_W (ICP_T / 64)
-#define ICP_MAXN 1024
-#define ICP_MAXF 2048
-#define ICP_MAXP 1024
 #define ICP_MAXIT 64
 #define ICP_TINY 1e-37f
 #define ICP_K 17                                               // count, sum p [3], sum q [3], sum q p^T [9], sum |p - q|^2
 
-// p q - r s from separately rounded products (no fma): the normal of a triangle with two equal corners, or with collinear corners whose
-// edges are exact multiples of each other, is exactly zero
-__device__ __forceinline__ float icp_det2(float p, float q, float r, float s) {
-#pragma clang fp contract(off)
-    return p * q - r * s;
-}
-
-// The association is written with its fused multiply-adds spelled out and contraction off, so that every kernel that inlines it rounds alike
-// whatever the compiler makes of the code around it: with contraction left to the compiler two kernels chose different operands to fuse,
-// and a near-tie between two triangles then fell to different sides.  The forms are the ones mesh_icp_kernel has always run.
-// x0 x1 + y0 y1 + z0 z1 as fma(y0, y1, x0 x1) + z0 z1: the facing test
-__device__ __forceinline__ float icp_dot3(float x0, float x1, float y0, float y1, float z0, float z1) {
-#pragma clang fp contract(off)
-    return __builtin_fmaf(y0, y1, x0 * x1) + z0 * z1;
-}
-// u . v as fma(uz, vz, fma(ux, vx, uy vy)): the walk's d1 .. d6 and |q - p|^2
-__device__ __forceinline__ float icp_dot(float ux, float uy, float uz, float vx, float vy, float vz) {
-#pragma clang fp contract(off)
-    return __builtin_fmaf(uz, vz, __builtin_fmaf(ux, vx, uy * vy));
-}
 // v ab + w ac - ap as fma(ac, w, ab v) - ap: a coordinate of q - p
 __device__ __forceinline__ float icp_comb(float v, float ab, float w, float ac, float ap) {
 #pragma clang fp contract(off)
@@ -142,31 +118,6 @@ __device__ __forceinline__ void icp_walk(const IcpShared& s, int count, float px
             if (BARY) { wa = near_a ? fmaxf(1.f - v - w, 0.f) : 0.f; wb = v; wc = w; }        // (1 - (1 - w) - w is not 0 for every w: hence near_a)
         }
     }
-}
-
-// v[0..K) summed over the block in a fixed order -> out[0..K) in LDS (ends in a barrier): the xor butterfly per wave, then thread k
-// adds the 16 wave partials of sum k as a balanced tree
-template <int K>
-__device__ __forceinline__ void icp_block_sum(double* v, double* sm, double* out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double r = wave_sum_d(v[k]);
-        if (lane == 0) sm[wave * K + k] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double p[ICP_W];
-#pragma unroll
-        for (int w = 0; w < ICP_W; ++w) p[w] = sm[w * K + threadIdx.x];
-#pragma unroll
-        for (int m = ICP_W / 2; m > 0; m /= 2) {
-#pragma unroll
-            for (int w = 0; w < m; ++w) p[w] = p[2 * w] + p[2 * w + 1];
-        }
-        out[threadIdx.x] = p[0];
-    }
-    __syncthreads();
 }
 
 // One step from the inlier sums a[]: composes it into xf (R row-major, t).  Returns false when the iteration stops.

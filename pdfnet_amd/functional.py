@@ -2451,7 +2451,8 @@ def mesh_penetration(verts, faces, return_fields=False):
 
 
 def _cloud_args(name, verts, faces, cloud, valid, trim):
-    """The checks `mesh_icp` and `cloud_mesh_loss` share -> (verts, faces, cloud, valid or None as detached contiguous f32 / int64 tensors,
+    """The checks `mesh_icp`, `cloud_mesh_loss` and `mesh_cloud_loss` share -> (verts, faces, cloud, valid or None as detached contiguous
+    f32 / int64 tensors,
     lead, n, Fc, P, trim)."""
     hip.require_gpu(verts, faces, cloud, valid)
     v, f, c = verts.detach().float().contiguous(), faces.detach().long().contiguous(), cloud.detach().float().contiguous()
@@ -2530,6 +2531,48 @@ def cloud_mesh_loss(verts, faces, cloud, valid=None, trim=0.03, return_fields=Fa
     return_fields: (loss, inliers int32 [..., 2], tri int32 [..., 2, P], bary [..., 2, P, 3], closest [..., 2, P, 3]).
     The contract is `pdf_cloud_mesh_loss`'s in pdfnet_hip.h.  n, P <= 1024, Fc <= 2048.  Deterministic."""
     out = _CloudMeshLoss.apply(verts, faces, cloud, valid, trim, bool(return_fields), torch.is_grad_enabled() and verts.requires_grad)
+    return out if return_fields else out[0]
+
+
+class _MeshCloudLoss(torch.autograd.Function):
+    """loss [..., 2] of `mesh_cloud_loss`; the kernel writes d loss / d verts in the forward launch when verts needs it."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, cloud, valid, trim, margin, fields, want_grad):
+        v, f, c, va, lead, n, Fc, P, trim = _cloud_args('mesh_cloud_loss', verts, faces, cloud, valid, trim)
+        margin = float(margin)
+        if not 0.0 <= margin < float('inf'):
+            raise ValueError("pdfnet_amd: mesh_cloud_loss takes a finite margin >= 0, got %r" % (margin,))
+        dev = v.device
+        loss = torch.empty(lead, dtype=torch.float32, device=dev)
+        inliers, visible = (torch.empty(lead, dtype=torch.int32, device=dev) for _ in range(2))
+        grad = torch.empty_like(v) if want_grad else None
+        vis, nn = (torch.empty(lead + (n,), dtype=torch.int32, device=dev) for _ in range(2)) if fields else (None, None)
+        _L().pdf_mesh_cloud_loss(ptr(v), ptr(f), ptr(c), ptr(va), loss.numel() // 2, n, Fc, P, trim, margin, ptr(loss), ptr(inliers), ptr(visible),
+                                 ptr(grad), ptr(vis), ptr(nn), stream())
+        ctx.grad, ctx.dtype = grad, verts.dtype
+        extra = (inliers, visible, vis, nn) if fields else (inliers, visible)
+        ctx.mark_non_differentiable(*extra)
+        return (loss,) + extra
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *unused):
+        return (g[..., None, None] * ctx.grad).to(ctx.dtype), None, None, None, None, None, None, None
+
+
+def mesh_cloud_loss(verts, faces, cloud, valid=None, trim=0.03, margin=0.002, return_fields=False):
+    """verts [..., 2, n, 3], faces [2, Fc, 3], cloud [..., 2, P, 3], valid [..., 2] or None as `mesh_icp` takes them -> loss [..., 2] in m^2: per
+    hand the mean of |v - p|^2 over the vertices v that the camera sees and whose nearest sensor point p of that hand is closer than `trim`.
+    A vertex is seen when it is a corner of a camera-facing triangle of its hand and the ray from it to the camera meets no camera-facing
+    triangle of either hand (its own incident triangles apart; the other hand only when that hand is valid) more than `margin` metres away
+    from it.  This is the direction `cloud_mesh_loss` lacks: surface predicted where the sensor saw none is pulled back, while a vertex
+    behind the other hand or on the far side of its own is left alone; 0 without an inlier or with valid = 0.
+    Differentiable once, with respect to `verts` only: an inlier vertex receives (2/m)(v - p), with the visibility, the match and the number
+    m of inliers held constant.  The gradient comes out of the forward launch; backward is one multiplication.
+    return_fields: (loss, inliers int32 [..., 2], visible int32 [..., 2], vis int32 [..., 2, n], nn int32 [..., 2, n]: the matched point, -1
+    without one).  The contract is `pdf_mesh_cloud_loss`'s in pdfnet_hip.h.  n, P <= 1024, Fc <= 2048.  Deterministic."""
+    out = _MeshCloudLoss.apply(verts, faces, cloud, valid, trim, margin, bool(return_fields), torch.is_grad_enabled() and verts.requires_grad)
     return out if return_fields else out[0]
 
 

@@ -624,7 +624,8 @@ class Trainer:
         return tot / max(n, 1)
 
 
-    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False, rendered=False, refined=False):
+    def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False, rendered=False, refined=False,
+                   two_sided=False):
         """Counterpart of `BaseTrainer.evaluation` (lib/trains/base_trainer.py:207-429, H2O branch): the test-mode pass
         (centres from the predicted heat-map, root from the predicted depth) and the mean Euclidean errors per hand --
         absolute and root-relative joints / vertices in mm, 2-D landmarks in pixels.  The reference evaluates on rank 0
@@ -651,7 +652,11 @@ class Trainer:
         refined:    False, True (= 'translation') or 'rigid': also what the depth measurement can still correct -- each predicted hand is moved
                     onto its sensor point cloud batch['cloud'] [B, 2, P, 3] (camera-space metres, `F.depth2pcl`'s) by `F.mesh_icp`, with a
                     translation or a rigid motion per iteration, and the absolute errors are taken again: the keys of `finish_refined`.  One
-                    more accumulator in the same buffer; needs `faces_pair`.  The other keys do not change."""
+                    more accumulator in the same buffer; needs `faces_pair`.  The other keys do not change.
+        two_sided:  also the trimmed, occlusion-aware Chamfer distance between the absolute meshes and the sensor point cloud batch['cloud']:
+                    cloud to mesh (`F.mesh_icp` with iters = 0) and mesh to cloud over the vertices the camera sees (`F.mesh_cloud_loss`), for
+                    the prediction and, as the sensor's own floor, for the ground truth -- the keys of `finish_two_sided`.  One more
+                    accumulator in the same buffer; needs `faces_pair`.  The other keys do not change."""
         if refined not in (False, True, 'translation', 'rigid'):
             raise ValueError("Trainer.evaluation: refined is False, True, 'translation' or 'rigid', got %r" % (refined,))
         mwl = self.model_with_loss
@@ -671,6 +676,8 @@ class Trainer:
                 acc4 = torch.zeros(8, dtype=torch.float64, device=dev)    # see rendered_sums
             if refined:
                 acc5 = torch.zeros(REFINED_SUMS, dtype=torch.float64, device=dev)      # see refined_sums
+            if two_sided:
+                acc6 = torch.zeros(TWO_SIDED_SUMS, dtype=torch.float64, device=dev)    # see two_sided_sums
             poses = []
             with torch.no_grad():
                 for batch in loader:
@@ -687,6 +694,8 @@ class Trainer:
                         acc4 += rendered_sums(tup, batch, mwl.loss.faces_pair)
                     if refined:
                         acc5 += refined_sums(tup, batch, mwl.loss.faces_pair, refined == 'rigid')
+                    if two_sided:
+                        acc6 += two_sided_sums(tup, batch, mwl.loss.faces_pair)
                     if json_path is not None:
                         if 'id' not in batch or 'frame_num' not in batch:
                             raise KeyError("Trainer.evaluation: hand_poses.json needs batch['id'] and batch['frame_num'] (interhand.py H2O entries)")
@@ -696,6 +705,9 @@ class Trainer:
                         poses.append(torch.cat((key, jp.reshape(jp.shape[0], -1).double()), 1))          # [B, 2 + 126]
             if aligned:                                            # one buffer for the reduction and the copy (the counts are exact in float64)
                 acc = torch.cat((acc, acc2, pck.reshape(-1).double()))
+            if two_sided:                                          # before the refined block
+                tt = acc.numel()
+                acc = torch.cat((acc, acc6))
             if refined:                                            # before the interaction block, which is read from the end
                 rt = acc.numel()
                 acc = torch.cat((acc, acc5))
@@ -716,6 +728,8 @@ class Trainer:
                 out.update(finish_rendered(acc[at:at + 8]))
             if refined:
                 out.update(finish_refined(acc[rt:rt + REFINED_SUMS]))
+            if two_sided:
+                out.update(finish_two_sided(acc[tt:tt + TWO_SIDED_SUMS]))
             if json_path is not None:
                 rows = torch.cat(poses) if poses else torch.zeros((0, 128), dtype=torch.float64, device=dev)
                 if self.world > 1:                                 # ragged gather: pad every rank's block to the longest
@@ -1015,6 +1029,64 @@ def write_refined_scores(path, ev):
     with open(path, 'a') as fo:
         fo.write('eval refined \n')
         for k in REFINED_KEYS:
+            if k in ev:
+                fo.write('%s: %.2f\n' % (k, ev[k]))
+
+
+TWO_SIDED_KEYS = ('mesh_cloud_mm', 'gt_mesh_cloud_mm', 'cloud_mesh_mm', 'chamfer_mm', 'visible_share', 'covered_share', 'two_sided_samples')
+TWO_SIDED_SUMS = 21
+TWO_SIDED_MARGIN = 0.002                     # metres: how far in front of a vertex an occluder must lie to hide it
+
+
+def two_sided_sums(tup, batch, faces):
+    """test-mode 9-tuple, the batch (`cloud` [B, 2, P, 3] camera-space metres, `valid` [B, 2]) and the faces [2, Fc, 3] -> float64 [21] on the
+    device.  `F.mesh_cloud_loss` (REFINE_TRIM, TWO_SIDED_MARGIN) on the predicted and on the ground-truth absolute vertices, and the cloud-to-mesh
+    residual of the prediction as `refined_sums` takes it (`F.mesh_icp`, iters = 0).  [0] the number of samples; then, per quantity, the pair
+    (left, right) of sums over the samples with that hand valid (valid == 1): [1:3] the root mean square distance of the prediction's inlier
+    vertices to the cloud, [3:5] its visible vertices / n, [5:7] its inliers / its visible vertices (0 without any), [7:9] the root mean square
+    distance of the ground truth's inlier vertices, [9:11] that of the cloud's inliers to the predicted mesh, [11:13] the number of such
+    samples, and those of them [13:15] with an inlier vertex, [15:17] with a visible vertex, [17:19] with an inlier vertex of the ground
+    truth, [19:21] with an inlier point (what the means are over)."""
+    vp, vg = tup[0], tup[2]
+    if 'cloud' not in batch:
+        raise KeyError("Trainer.evaluation: two_sided needs batch['cloud'], the hands' sensor points [B, 2, P, 3] in camera-space metres "
+                       "(F.depth2pcl, interhand.py H2O entries)")
+    cloud, valid = batch['cloud'], batch['valid']
+    lp, ip, sp = F.mesh_cloud_loss(vp, faces, cloud, valid=valid, trim=REFINE_TRIM, margin=TWO_SIDED_MARGIN, return_fields=True)[:3]
+    lg, ig = F.mesh_cloud_loss(vg, faces, cloud, valid=valid, trim=REFINE_TRIM, margin=TWO_SIDED_MARGIN, return_fields=True)[:2]
+    _, _, _, rms0, in0 = F.mesh_icp(vp, faces, cloud, valid=valid, iters=0, trim=REFINE_TRIM)
+    has = valid == 1                                                                             # [B, 2]
+    ones = torch.ones(has.shape, dtype=torch.float64, device=vp.device)
+    terms = torch.stack((lp.double().sqrt(), sp.double() / vp.shape[-2], ip.double() / sp.double().clamp(min=1), lg.double().sqrt(), rms0.double(),
+                         ones, (ip > 0).double(), (sp > 0).double(), (ig > 0).double(), (in0 > 0).double()))      # [10, B, 2]
+    n = torch.full((1,), float(vp.shape[0]), dtype=torch.float64, device=vp.device)
+    return torch.cat((n, torch.where(has, terms, torch.zeros_like(terms)).sum(1).reshape(-1)))
+
+
+def finish_two_sided(acc):
+    """The accumulator of `two_sided_sums` -> 'mesh_cloud_mm' (root mean square distance of the predicted mesh's visible inlier vertices to the
+    cloud, mean over the hands with one), 'gt_mesh_cloud_mm' (the same on the annotation: the sensor's own floor), 'cloud_mesh_mm' (the other
+    direction: `finish_refined`'s 'cloud_res_mm'), 'chamfer_mm' (the mean of the two directions of the prediction), 'visible_share' (visible
+    vertices / n, mean over the valid hands), 'covered_share' (inliers / visible vertices, mean over the hands with a visible vertex),
+    'two_sided_samples'.  A mean over nothing is 0; without a sample only 'two_sided_samples'."""
+    a = [float(x) for x in acc]
+    out = {'two_sided_samples': int(round(a[0]))}
+    if out['two_sided_samples'] == 0:
+        return out
+    mean = lambda total, count: total / count if round(count) > 0 else 0.0
+    res = {'mesh_cloud_mm': mean(a[1] + a[2], a[13] + a[14]) * 1000, 'gt_mesh_cloud_mm': mean(a[7] + a[8], a[17] + a[18]) * 1000,
+           'cloud_mesh_mm': mean(a[9] + a[10], a[19] + a[20]) * 1000, 'visible_share': mean(a[3] + a[4], a[11] + a[12]),
+           'covered_share': mean(a[5] + a[6], a[15] + a[16])}
+    res['chamfer_mm'] = (res['cloud_mesh_mm'] + res['mesh_cloud_mm']) / 2
+    res.update(out)
+    return {k: res[k] for k in TWO_SIDED_KEYS}
+
+
+def write_two_sided_scores(path, ev):
+    """Append the figures of `evaluation(two_sided=True)` that are there as a block of their own (`key: %.2f`, like `write_refined_scores`)."""
+    with open(path, 'a') as fo:
+        fo.write('eval two-sided \n')
+        for k in TWO_SIDED_KEYS:
             if k in ev:
                 fo.write('%s: %.2f\n' % (k, ev[k]))
 

@@ -73,19 +73,31 @@ def projection_batch(scale, trans2d, pts, img_size):
     return s * pts[..., :2] + t
 
 
+def _cloud_verts(vp, root, ind, batch, input_res, down_ratio, weight_name):
+    """What the two cloud terms share -> (the absolute predicted vertices [B, 2, 778, 3], batch['valid']); KeyError without batch['cloud']."""
+    if 'cloud' not in batch:
+        raise KeyError("CtdetLoss: %s > 0 needs batch['cloud'], the hands' sensor points [B, 2, P, 3] in camera-space metres "
+                       "(F.depth2pcl, interhand.py H2O entries)" % weight_name)
+    root_pred = uv_root_3d(ind.t(), root[..., 1:] / 100, 0.4 + root[..., 0] / 100, batch['K_new'], input_res, down_ratio)
+    return (vp + root_pred).transpose(0, 1).contiguous(), batch['valid']
+
+
 def cloud_term(vp, root, ind, batch, faces, input_res, down_ratio=4, trim=0.03):
     """The cloud-to-mesh training term -> [B] in mm^2: sum over the valid hands of `F.cloud_mesh_loss` (the mean squared distance from the hand's
     sensor points within `trim` metres to the camera-facing surface of its predicted mesh), times 1e6.
     vp [2, B, 778, 3] root-relative predicted vertices and root [2, B, 3] the predicted root parameters, both (left, right) as the mesh terms
     take them; the absolute vertices are vp + uv_root_3d(...) with the batch's `ind`, as in abs_verts_loss.  batch: `cloud` [B, 2, P, 3]
     camera-space metres, `valid` [B, 2], `K_new`; faces [2, Fc, 3].  Needs no annotation; differentiable in vp and root."""
-    if 'cloud' not in batch:
-        raise KeyError("CtdetLoss: cloud_weight > 0 needs batch['cloud'], the hands' sensor points [B, 2, P, 3] in camera-space metres "
-                       "(F.depth2pcl, interhand.py H2O entries)")
-    valid = batch['valid']
-    root_pred = uv_root_3d(ind.t(), root[..., 1:] / 100, 0.4 + root[..., 0] / 100, batch['K_new'], input_res, down_ratio)
-    verts = (vp + root_pred).transpose(0, 1).contiguous()                                                   # [B, 2, 778, 3]
+    verts, valid = _cloud_verts(vp, root, ind, batch, input_res, down_ratio, 'cloud_weight')
     return 1e6 * (valid * F.cloud_mesh_loss(verts, faces, batch['cloud'], valid=valid, trim=trim)).sum(1)
+
+
+def mesh_cloud_term(vp, root, ind, batch, faces, input_res, down_ratio=4, trim=0.03, margin=0.002):
+    """The mesh-to-cloud training term -> [B] in mm^2: sum over the valid hands of `F.mesh_cloud_loss` (the mean squared distance from the
+    vertices of the predicted mesh that the camera sees to their nearest sensor points within `trim` metres), times 1e6.  The arguments and
+    the absolute vertices are `cloud_term`'s; with it this is a trimmed, occlusion-aware Chamfer loss on the sensor cloud."""
+    verts, valid = _cloud_verts(vp, root, ind, batch, input_res, down_ratio, 'mesh_cloud_weight')
+    return 1e6 * (valid * F.mesh_cloud_loss(verts, faces, batch['cloud'], valid=valid, trim=trim, margin=margin)).sum(1)
 
 
 FORK_DENSE_LOSS = os.environ.get("PDFNET_FORK_DENSE_LOSS", "1") != "0"
@@ -94,7 +106,8 @@ FORK_DENSE_LOSS = os.environ.get("PDFNET_FORK_DENSE_LOSS", "1") != "0"
 class CtdetLoss(nn.Module):
     """opt fields used: size_train, center_weight (200), reproj_weight (1), bone_dir_weight (200), down_ratio (4), cloud_weight (0: the
     cloud-to-mesh term `cloud_term` is neither computed nor launched; > 0: train mode adds cloud_weight * cloud_loss and reports
-    stats['cloud_loss']), cloud_trim (0.03 m).
+    stats['cloud_loss']), mesh_cloud_weight (0; > 0: likewise mesh_cloud_weight * `mesh_cloud_term`, stats['mesh_cloud_loss']), cloud_trim (0.03 m,
+    both terms), cloud_margin (0.002 m: how far in front of a vertex an occluder must lie to hide it).
     `consts`: {'full_regressor_left/right' [21,778], 'faces_left/right' [1538,3] int64}."""
 
     def __init__(self, opt, consts):
@@ -137,6 +150,13 @@ class CtdetLoss(nn.Module):
                             getattr(self.opt, 'down_ratio', 4), getattr(self.opt, 'cloud_trim', 0.03))
             loss = loss + cw * cl
             stats['cloud_loss'] = cl
+            stats['loss'] = loss
+        mw = getattr(self.opt, 'mesh_cloud_weight', 0)
+        if mw > 0:                                           # the other direction: the vertices the camera sees against the measured depth
+            ml = mesh_cloud_term(_pair(result['verts3d']), _pair(paramsDict['root']), ind, batch, self.faces_pair, int(self.opt.size_train[0]),
+                                 getattr(self.opt, 'down_ratio', 4), getattr(self.opt, 'cloud_trim', 0.03), getattr(self.opt, 'cloud_margin', 0.002))
+            loss = loss + mw * ml
+            stats['mesh_cloud_loss'] = ml
             stats['loss'] = loss
         return loss, stats, None, None
 
