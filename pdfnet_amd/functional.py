@@ -840,7 +840,10 @@ class _Linear(Function):
                 _, oa = _O(op0_bf16=ptr(x16), op1_bf16=ptr(g16), in_scale=ptr(aff[0]) if aff is not None else None,
                            in_shift=ptr(aff[1]) if aff is not None else None)
                 L.pdf_linear_bwd_weight_x(ptr(x), ptr(g), ptr(out), ptr(out_b), ptr(ws), n, M, Nn, K, K, Nn, acc, stream(), oa)
-        dw, db = _param_grads(ctx, x, g, w, w_par, b_par, has_b, launch_w, Nn, M, 2.0 * M * Nn * K, fused_bias=True, shadows=(x16, g16))
+        # (a lazy BatchNorm's scale / shift are read by the weight-gradient kernel too: side-stream inputs like x and g.  They die with this
+        # node, and unrecorded the allocator hands their memory to the next launch of this stream while the side stream has yet to read it)
+        dw, db = _param_grads(ctx, x, g, w, w_par, b_par, has_b, launch_w, Nn, M, 2.0 * M * Nn * K, fused_bias=True,
+                              shadows=(x16, g16) + (tuple(aff) if aff is not None else ()))
         return dx, dw, db, None, None, None
 
 

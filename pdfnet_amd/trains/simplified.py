@@ -131,12 +131,16 @@ class CtdetLoss(nn.Module):
         # dense-map terms on a forked stream (round 6): two launches forward and one backward that neither feed nor need the mesh terms -- they and
         # their backward (which hands its gradients to the dense decoders' own streams) leave the main chain (PDFNET_FORK_DENSE_LOSS=0: in line, last)
         fd = F.fork(lambda: self.dense_terms(otherInfo, batch)) if (FORK_DENSE_LOSS and not test) else None
-        t = self.mesh_terms(result, paramsDict, handDictList, otherInfo['converter_left'], otherInfo['converter_right'],
-                            batch, ind, test, epoch)
+        try:
+            t = self.mesh_terms(result, paramsDict, handDictList, otherInfo['converter_left'], otherInfo['converter_right'],
+                                batch, ind, test, epoch)
+        finally:
+            # (also when mesh_terms raises: an unjoined fork keeps its slot of the stream pool for good -- ADVICE r6)
+            dense = fd.join() if fd is not None else None
         if test:
             return t
         # (in line: created last, so that their backward is issued first, ahead of the launch-bound mesh terms)
-        t.update(fd.join() if fd is not None else self.dense_terms(otherInfo, batch))
+        t.update(dense if fd is not None else self.dense_terms(otherInfo, batch))
         mp = t.pop('_mesh_part', None)
         if mp is not None:                                   # fused mesh terms: their weighted sum came out of the kernel
             loss = mp + self.dense_part(t)
