@@ -512,6 +512,41 @@ int pdf_cloud_mesh_loss(const float* verts, const long long* faces, const float*
  * no atomics, no scratch memory: two runs are bit-identical and a row depends only on the two hands of its own sample. */
 int pdf_mesh_cloud_loss(const float* verts, const long long* faces, const float* cloud, const float* valid, int B, int n, int Fc, int P, float trim,
                         float margin, float* loss, int* inliers, int* visible, float* grad, int* vis, int* nn, void* stream);
+/* Differentiable inter-hand penetration loss (csrc/penetration.hip).  Row (b, h): every vertex of hand h of sample b against the triangle mesh
+ * of the OTHER hand of that sample (vertices verts[b][1-h], triangles faces[1-h], all of them, not only the camera-facing ones): the mean
+ * squared distance from the vertices that are inside the other hand to its surface, and its gradient with respect to BOTH meshes.
+ * verts [B,2,n,3] f32 metres (|coordinate| < 1e6); faces [2,Fc,3] int64, the tensor pdf_mesh_penetration takes (left, right), both hands
+ * oriented outwards; an index outside [0, n) is clamped; valid [B,2] f32 or NULL.  A row is live only when BOTH hands of its sample are valid
+ * (NULL: all are).
+ *   Inside    vertex i is inside when its generalized winding number with respect to the other mesh is > 0.5.  It is evaluated by the
+ *             expressions of pdf_mesh_penetration (the same per-triangle forms, atan2f, double accumulation in ascending face order), so
+ *             `inside` equals that entry point's wind > 0.5 bit for bit and `count` equals its count.
+ *   Closest   for an inside vertex v, q = the closest point of the other mesh's surface, by the device code of pdf_mesh_icp's association: the
+ *             seven regions in its order (vertex a, vertex b, edge ab, vertex c, edge ac, edge bc, face), fp32; a strictly smaller squared
+ *             distance replaces the best, so the lowest face index wins a tie.  A zero-area triangle is a candidate, as the segment or point it
+ *             is.  q = w_a a + w_b b + w_c c with pdf_cloud_mesh_loss's weights: exactly one-hot in a vertex region, exactly 0 for the
+ *             opposite corner in an edge region, every weight in [0, 1].
+ *   loss       [B,2] f32: (1/n) sum over the inside vertices of |v - q|^2, in m^2; summed in double in ascending vertex order by the
+ *              fixed-order block reduction of pdf_mesh_icp.  The divisor is n, not the inside count: the loss goes to 0 continuously as a
+ *              vertex leaves the other hand.
+ *   count      [B,2] int32: the inside vertices
+ *   grad_self  [B,2,n,3] f32 or NULL: d loss[b,h] / d verts[b,h]: (2/n)(v - q) on an inside vertex, exactly 0 elsewhere.
+ *   grad_other [B,2,n,3] f32 or NULL: d loss[b,h] / d verts[b,1-h], stored in row (b, h) and indexed by the OTHER hand's vertices.  The
+ *              envelope theorem (q is the minimiser over the triangle, so only the explicit dependence of q on the corners counts) gives
+ *              d |v - q|^2 / d a = -2 w_a (v - q), likewise for b and c: for every inside vertex, corner k of its triangle receives
+ *              -(2/n) w_k (v - q).  A vertex that no inside vertex's triangle touches gets exactly 0.  The contributions to a vertex are added
+ *              in ascending vertex order, in double.
+ *              The inside set and the association are held constant (they are piecewise constant); no gradient goes through the winding number.
+ *   inside     [B,2,n] int32 or NULL: 1 or 0
+ *   tri        [B,2,n] int32 or NULL: the face index in faces[1-h]; -1 for a vertex that is not inside
+ *   bary, closest [B,2,n,3] f32 or NULL: (w_a, w_b, w_c), the corners in the face's own order, and q; (0, 0, 0) where tri = -1
+ * A row that is not live: every output of the row is 0 and tri is -1.
+ * 1 <= n <= 1024, 1 <= Fc <= 2048, verts, faces, loss and count not NULL, else PDF_E_BADARG with nothing launched; B <= 0 returns 0.  Finite
+ * input gives finite output.  One launch, one workgroup per row, no atomics, no scratch memory: two runs are bit-identical and a row depends
+ * only on the two hands of its own sample. */
+int pdf_penetration_loss(const float* verts, const long long* faces, const float* valid, int B, int n, int Fc,
+                         float* loss, int* count, float* grad_self, float* grad_other,
+                         int* inside, int* tri, float* bary, float* closest, void* stream);
 
 /* ---- hand renderer (csrc/render.hip) ------------------------------------------------------------ */
 /* Forward-only z-buffered rasteriser of both hands of every sample under that sample's pinhole camera (the reference's pytorch3d

@@ -2579,6 +2579,60 @@ def mesh_cloud_loss(verts, faces, cloud, valid=None, trim=0.03, margin=0.002, re
     return out if return_fields else out[0]
 
 
+class _PenetrationLoss(torch.autograd.Function):
+    """loss [..., 2] of `penetration_loss`; the kernel writes both gradients (with respect to the hand's own vertices and to the other hand's) in
+    the forward launch when verts needs them."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, valid, fields, want_grad):
+        hip.require_gpu(verts, faces, valid)
+        v, f = verts.detach().float().contiguous(), faces.detach().long().contiguous()
+        if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
+            raise ValueError("pdfnet_amd: penetration_loss wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
+        lead, n, Fc = v.shape[:-2], v.shape[-2], f.shape[1]
+        if not (1 <= n <= 1024 and 1 <= Fc <= 2048):
+            raise ValueError("pdfnet_amd: penetration_loss takes 1 to 1024 vertices and 1 to 2048 faces per hand, got %d and %d" % (n, Fc))
+        va = None
+        if valid is not None:
+            va = valid.detach().float().contiguous()
+            if va.shape != lead:
+                raise ValueError("pdfnet_amd: penetration_loss wants valid %s, got %s" % (tuple(lead), tuple(va.shape)))
+        dev = v.device
+        loss, count = torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev)
+        grad_self, grad_other = (torch.empty_like(v), torch.empty_like(v)) if want_grad else (None, None)
+        inside, tri = (torch.empty(lead + (n,), dtype=torch.int32, device=dev) for _ in range(2)) if fields else (None, None)
+        bary, closest = (torch.empty_like(v), torch.empty_like(v)) if fields else (None, None)
+        _L().pdf_penetration_loss(ptr(v), ptr(f), ptr(va), loss.numel() // 2, n, Fc, ptr(loss), ptr(count), ptr(grad_self), ptr(grad_other),
+                                  ptr(inside), ptr(tri), ptr(bary), ptr(closest), stream())
+        ctx.grads, ctx.dtype = (grad_self, grad_other), verts.dtype
+        extra = (count, inside, tri, bary, closest) if fields else (count,)
+        ctx.mark_non_differentiable(*extra)
+        return (loss,) + extra
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *unused):
+        grad_self, grad_other = ctx.grads
+        w = g[..., None, None]
+        return (w * grad_self + (w * grad_other).flip(-3)).to(ctx.dtype), None, None, None, None
+
+
+def penetration_loss(verts, faces, valid=None, return_fields=False):
+    """verts [..., 2, n, 3] metres (left, right hand), faces [2, Fc, 3] int64 (the loss module's `faces_pair`, oriented outwards) as
+    `mesh_penetration` takes them, valid [..., 2] or None -> loss [..., 2] in m^2: per hand (1/n) sum |v - q|^2 over its vertices v that are
+    inside the OTHER hand's mesh (generalized winding number > 0.5: `mesh_penetration`'s rule, by the same expressions), q their closest
+    points of the other hand's surface (`mesh_icp`'s seven-region association over all triangles); 0 for a sample that lacks a valid hand and
+    for hands that do not intersect.  The divisor is n: the loss falls to 0 continuously as a vertex leaves the other hand.
+    Differentiable once, with respect to `verts` only, towards BOTH hands: an inside vertex receives (2/n)(v - q) and corner k of its triangle
+    on the other hand -(2/n) w_k (v - q), with the inside set and the association held constant (no gradient through the winding number).
+    Both gradients come out of the forward launch; backward is g * grad_self + (g * grad_other) with the two hands swapped.
+    return_fields: (loss, count int32 [..., 2], inside int32 [..., 2, n], tri int32 [..., 2, n]: the face of the other hand, -1 for a vertex
+    that is not inside, bary [..., 2, n, 3], closest [..., 2, n, 3]).  The contract is `pdf_penetration_loss`'s in pdfnet_hip.h.
+    n <= 1024, Fc <= 2048.  Deterministic."""
+    out = _PenetrationLoss.apply(verts, faces, valid, bool(return_fields), torch.is_grad_enabled() and verts.requires_grad)
+    return out if return_fields else out[0]
+
+
 # ----------------------------------------------------------------------------------------------
 # Hand renderer (csrc/render.hip): the reference's pytorch3d MeshRasterizer + HardPhongShader (mano_utils.py:44-156) as a tile rasteriser.
 RENDER_MAX_DEGREE = 32

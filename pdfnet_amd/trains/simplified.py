@@ -73,13 +73,18 @@ def projection_batch(scale, trans2d, pts, img_size):
     return s * pts[..., :2] + t
 
 
+def _abs_verts(vp, root, ind, batch, input_res, down_ratio):
+    """What the geometric terms share -> (the absolute predicted vertices [B, 2, 778, 3], batch['valid'])."""
+    root_pred = uv_root_3d(ind.t(), root[..., 1:] / 100, 0.4 + root[..., 0] / 100, batch['K_new'], input_res, down_ratio)
+    return (vp + root_pred).transpose(0, 1).contiguous(), batch['valid']
+
+
 def _cloud_verts(vp, root, ind, batch, input_res, down_ratio, weight_name):
-    """What the two cloud terms share -> (the absolute predicted vertices [B, 2, 778, 3], batch['valid']); KeyError without batch['cloud']."""
+    """What the two cloud terms share -> `_abs_verts`; KeyError without batch['cloud']."""
     if 'cloud' not in batch:
         raise KeyError("CtdetLoss: %s > 0 needs batch['cloud'], the hands' sensor points [B, 2, P, 3] in camera-space metres "
                        "(F.depth2pcl, interhand.py H2O entries)" % weight_name)
-    root_pred = uv_root_3d(ind.t(), root[..., 1:] / 100, 0.4 + root[..., 0] / 100, batch['K_new'], input_res, down_ratio)
-    return (vp + root_pred).transpose(0, 1).contiguous(), batch['valid']
+    return _abs_verts(vp, root, ind, batch, input_res, down_ratio)
 
 
 def cloud_term(vp, root, ind, batch, faces, input_res, down_ratio=4, trim=0.03):
@@ -100,6 +105,16 @@ def mesh_cloud_term(vp, root, ind, batch, faces, input_res, down_ratio=4, trim=0
     return 1e6 * (valid * F.mesh_cloud_loss(verts, faces, batch['cloud'], valid=valid, trim=trim, margin=margin)).sum(1)
 
 
+def penetration_term(vp, root, ind, batch, faces, input_res, down_ratio=4):
+    """The inter-hand penetration training term -> [B] in mm^2: the sum over the two hands of `F.penetration_loss` (the squared distance from
+    the hand's predicted vertices that lie inside the other predicted hand to that hand's surface, summed and divided by 778), times 1e6; 0 for
+    a sample without two valid hands.  vp, root, ind, faces and the absolute vertices are `cloud_term`'s; batch: `valid` [B, 2], `K_new`.
+    Needs neither annotation nor sensor data; differentiable in vp and root of BOTH hands: it pushes the inside vertices out and the
+    surface they are under away, so it is the one geometric term that acts on the hands' relative placement."""
+    verts, valid = _abs_verts(vp, root, ind, batch, input_res, down_ratio)
+    return 1e6 * F.penetration_loss(verts, faces, valid=valid).sum(1)
+
+
 FORK_DENSE_LOSS = os.environ.get("PDFNET_FORK_DENSE_LOSS", "1") != "0"
 
 
@@ -107,7 +122,9 @@ class CtdetLoss(nn.Module):
     """opt fields used: size_train, center_weight (200), reproj_weight (1), bone_dir_weight (200), down_ratio (4), cloud_weight (0: the
     cloud-to-mesh term `cloud_term` is neither computed nor launched; > 0: train mode adds cloud_weight * cloud_loss and reports
     stats['cloud_loss']), mesh_cloud_weight (0; > 0: likewise mesh_cloud_weight * `mesh_cloud_term`, stats['mesh_cloud_loss']), cloud_trim (0.03 m,
-    both terms), cloud_margin (0.002 m: how far in front of a vertex an occluder must lie to hide it).
+    both terms), cloud_margin (0.002 m: how far in front of a vertex an occluder must lie to hide it), penetration_weight (0: the inter-hand
+    penetration term `penetration_term` is neither computed nor launched; > 0: train mode adds penetration_weight * penetration_loss, after
+    the two cloud terms, and reports stats['penetration_loss']; it needs no batch['cloud']).
     `consts`: {'full_regressor_left/right' [21,778], 'faces_left/right' [1538,3] int64}."""
 
     def __init__(self, opt, consts):
@@ -161,6 +178,13 @@ class CtdetLoss(nn.Module):
                                  getattr(self.opt, 'down_ratio', 4), getattr(self.opt, 'cloud_trim', 0.03), getattr(self.opt, 'cloud_margin', 0.002))
             loss = loss + mw * ml
             stats['mesh_cloud_loss'] = ml
+            stats['loss'] = loss
+        pw = getattr(self.opt, 'penetration_weight', 0)
+        if pw > 0:                                           # repulsion: the vertices of one predicted hand that lie inside the other
+            pl = penetration_term(_pair(result['verts3d']), _pair(paramsDict['root']), ind, batch, self.faces_pair, int(self.opt.size_train[0]),
+                                  getattr(self.opt, 'down_ratio', 4))
+            loss = loss + pw * pl
+            stats['penetration_loss'] = pl
             stats['loss'] = loss
         return loss, stats, None, None
 
