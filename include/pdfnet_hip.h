@@ -159,7 +159,8 @@ int pdf_scatter_rows_add(const float* dout, int ldo, int C, long HW, const long*
 int pdf_window_op(float* feat, int ldf, int C, int H, int W, const long* ind, long ind_bstride,
                   int B, int M, int r, float* buf, const float* src, int mode, void* stream);
 /* centre decode of the test path: _nms(5x5) + _topk(K=1) per (sample, channel) map (intaghand_encoder.py:349-367,750-758;
- * lib/trains/simplified.py:378-384).  hm [BC][H][W] plain, ind int64 [BC], score [BC] or NULL. */
+ * lib/trains/simplified.py:378-384).  hm [BC][H][W] plain, ind int64 [BC], score [BC] or NULL.  0 <= ind < H * W whatever hm holds: a NaN
+ * never wins, and a map of NaN alone gives index 0 with score NaN. */
 int pdf_nms_top1(const float* hm, int BC, int H, int W, long* ind, float* score, void* stream);
 /* nn.MaxPool2d((1,K)) / ((S2,1)) of netR_1/2/3 (intaghand_encoder.py:62,82,100): x [R][K][ldx] -> y [R][ldy], arg [R][C] */
 int pdf_maxk_fwd(const float* x, int ldx, int C, long R, int K, float* y, int ldy, int* arg, void* stream);
@@ -332,7 +333,9 @@ int pdf_dropout(const float* x, float* y, long n, float p, unsigned long long se
 /* y = res + dropout(x) (residual tails, self_attn.py:31-33,80-84); backward: d res = dy, dx = pdf_dropout(dy, same seed) */
 int pdf_dropout_add(const float* x, const float* res, float* y, long n, float p, unsigned long long seed,
                     const unsigned long long* step, void* stream);
-/* resnet.maxpool (resnet.py:206).  bwd: when C % 4 == 0 and the pointers are 16-byte aligned every dx element is written exactly once
+/* resnet.maxpool (resnet.py:206).  arg [N][OH][OW][C] holds the winning tap ky * 3 + kx of each window and is ALWAYS in bounds: the scan
+ * starts at the window's first in-bounds tap and takes a NaN like a larger value (torch.max_pool2d), so an all -inf window or a NaN
+ * cannot leave a tap in the padding, and y carries NaN.  bwd: when C % 4 == 0 and the pointers are 16-byte aligned every dx element is written exactly once
  * (gather over the <= 4 windows of an input element); otherwise dx must be zero-filled by the caller (atomic scatter). */
 int pdf_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, float* y, unsigned char* arg, void* stream);
 int pdf_maxpool3s2_bwd(const float* dy, const unsigned char* arg, int N, int H, int W, int C, float* dx, void* stream);

@@ -238,13 +238,17 @@ PDF_API int pdf_dropout_add(const float* x, const float* res, float* y, long n, 
 
 // ---------------------------------------------------------------------------------------------
 // MaxPool2d(3, stride 2, pad 1) on NHWC (resnet.maxpool, intaghand_encoder.py:716)
+// The arg-max starts at the window's first IN-BOUNDS tap (row / column 1 for the first output row / column, whose tap 0 lies in the
+// padding) and a NaN is taken like a larger value: what ATen does.  So arg names an in-bounds tap whatever the input holds (an all -inf
+// window, a NaN) -- the backward indexes dx with it -- and y carries NaN as torch.max_pool2d does.
+__device__ __forceinline__ int maxpool3s2_first_tap(int oy, int ox) { return (oy == 0 ? 3 : 0) + (ox == 0 ? 1 : 0); }
 __global__ void maxpool3s2_fwd_kernel(const float* __restrict__ x, int N, int H, int W, int C, int OH, int OW,
                                       float* __restrict__ y, unsigned char* __restrict__ arg, long total) {
     GRID_STRIDE(i, total) {
         int c = (int)(i % C); long p = i / C;
         int ox = (int)(p % OW); p /= OW;
         int oy = (int)(p % OH); int n = (int)(p / OH);
-        float best = -INFINITY; int bi = 0;
+        float best = -INFINITY; int bi = maxpool3s2_first_tap(oy, ox);
         for (int ky = 0; ky < 3; ++ky) {
             int iy = oy * 2 - 1 + ky;
             if (iy < 0 || iy >= H) continue;
@@ -252,7 +256,7 @@ __global__ void maxpool3s2_fwd_kernel(const float* __restrict__ x, int N, int H,
                 int ix = ox * 2 - 1 + kx;
                 if (ix < 0 || ix >= W) continue;
                 float v = x[(((long)n * H + iy) * W + ix) * C + c];
-                if (v > best) { best = v; bi = ky * 3 + kx; }
+                if (v > best || v != v) { best = v; bi = ky * 3 + kx; }
             }
         }
         y[i] = best; arg[i] = (unsigned char)bi;
@@ -267,7 +271,7 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd_v4_kernel(const float* __r
         const int ox = (int)(p % OW); p /= OW;
         const int oy = (int)(p % OH); const int n = (int)(p / OH);
         float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+        int b0 = maxpool3s2_first_tap(oy, ox), b1 = b0, b2 = b0, b3 = b0;
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             const int iy = oy * 2 - 1 + ky;
@@ -277,10 +281,10 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd_v4_kernel(const float* __r
                 if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
                 const float4 v = *reinterpret_cast<const float4*>(x + (((long)n * H + iy) * W + ix) * C + c);
                 const int t = ky * 3 + kx;
-                if (v.x > best.x) { best.x = v.x; b0 = t; }
-                if (v.y > best.y) { best.y = v.y; b1 = t; }
-                if (v.z > best.z) { best.z = v.z; b2 = t; }
-                if (v.w > best.w) { best.w = v.w; b3 = t; }
+                if (v.x > best.x || v.x != v.x) { best.x = v.x; b0 = t; }
+                if (v.y > best.y || v.y != v.y) { best.y = v.y; b1 = t; }
+                if (v.z > best.z || v.z != v.z) { best.z = v.z; b2 = t; }
+                if (v.w > best.w || v.w != v.w) { best.w = v.w; b3 = t; }
             }
         }
         *reinterpret_cast<float4*>(y + i * 4) = best;

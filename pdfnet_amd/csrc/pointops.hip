@@ -616,7 +616,12 @@ __global__ __launch_bounds__(256) void nms_top1_kernel(const float* __restrict__
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { ind[blockIdx.x] = si[0]; if (score) score[blockIdx.x] = sv[0]; }
+    if (threadIdx.x == 0) {
+        // a map of NaN alone wins no comparison: index 0 and its NaN instead of the 0x7fffffff start value (ind feeds row gathers)
+        const bool none = si[0] >= H * W;
+        ind[blockIdx.x] = none ? 0 : si[0];
+        if (score) score[blockIdx.x] = (none && H * W > 0) ? m[0] : sv[0];
+    }
 }
 
 PDF_API int pdf_nms_top1(const float* hm, int BC, int H, int W, long* ind, float* score, void* stream) {

@@ -712,18 +712,48 @@ def test_mano_split_coeff_decode_and_fix_shape(F):
 
 
 def test_adam(F):
+    """pdf_adam_step, three steps at n = 10000 (ragged sizes, offset pointers, the second loop trip, grad_scale, tiny and zero gradients:
+    tests/test_spatial_gpu.py).  This test used to be close(p, torch.optim.Adam in float32, 1e-7), whose bar is 1e-7 + 1e-5 * max|p| =
+    4.2e-5 while three steps at lr 1e-4 move p by only 3e-4: a kernel whose step is 13 % too large passed it (error 3.8e-5 in a CPU
+    emulation of a 1.13x step), and m and v were never read back.  Now, against textbook Adam in float64 fed the kernel's float32 inputs:
+      * from p0 = 0 (the displacement is the update) p, m and v elementwise within 2^-18 relative (3.8e-6) + 1e-30: the update has about
+        6 float32 roundings, a 1 % error in any factor exceeds the bar more than 2,000-fold;
+      * from p0 = randn |p - ref| <= steps * 2^-24 * max|p| (one rounding of p per step) + that bar on the displacement;
+      * against torch.optim.Adam in float64 with double constants the displacement from p0 = 0 within 2e-5 relative (float32 constants
+        alone shift it by 6.6e-6 on the CPU)."""
     from pdfnet_amd import hip
-    p0, g = rnd(10000, seed=1), rnd(10000, seed=2)
-    pr = p0.clone().requires_grad_()
-    opt = torch.optim.Adam([pr], lr=1e-4)
-    pd, m, v = dev(p0.clone()), dev(torch.zeros(10000)), dev(torch.zeros(10000))
-    for step in range(1, 4):
-        pr.grad = g * step
+    from tests.util import adam_float64
+    n, steps, hyper = 10000, 3, dict(lr=1e-4, b1=0.9, b2=0.999, eps=1e-8)
+    g = rnd(n, seed=2)
+    grads = [g * t for t in range(1, steps + 1)]
+    corrs = [torch.tensor([1 - 0.9 ** t, 1 - 0.999 ** t], dtype=torch.float32) for t in range(1, steps + 1)]
+
+    def run(p0):
+        pd, m, v = dev(p0.clone()), dev(torch.zeros(n)), dev(torch.zeros(n))
+        for gt, c in zip(grads, corrs):
+            gd, cd = dev(gt), dev(c)
+            hip.lib().pdf_adam_step(hip.ptr(pd), hip.ptr(gd), hip.ptr(m), hip.ptr(v), n, hyper["lr"], hyper["b1"], hyper["b2"], hyper["eps"],
+                                    hip.ptr(cd), 1.0, hip.stream())
+        return [t.cpu().double() for t in (pd, m, v)]
+
+    def rel(a, ref, bar, what):
+        worst = ((a - ref).abs() / (bar * ref.abs() + 1e-30)).max().item()
+        assert worst <= 1, "%s: %.2f times the bar" % (what, worst)
+    refs = adam_float64(torch.zeros(n), grads, corrs, **hyper)
+    outs = run(torch.zeros(n))
+    for name, a, r in zip("pmv", outs, refs):
+        rel(a, r, 2.0 ** -18, "adam %s" % name)
+    pt = torch.zeros(n, dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.Adam([pt], lr=1e-4)
+    for gt in grads:
+        pt.grad = gt.double()
         opt.step()
-        corr = dev(torch.tensor([1 - 0.9 ** step, 1 - 0.999 ** step]))
-        hip.lib().pdf_adam_step(hip.ptr(pd), hip.ptr(dev(g * step)), hip.ptr(m), hip.ptr(v), 10000, 1e-4, 0.9, 0.999, 1e-8,
-                                hip.ptr(corr), 1.0, hip.stream())
-    close(pd, pr, 1e-7, what="adam")
+    rel(outs[0], pt.detach(), 2e-5, "adam p against torch.optim.Adam")
+    p0 = rnd(n, seed=1)
+    pr = adam_float64(p0, grads, corrs, **hyper)[0]
+    err = (run(p0)[0] - pr).abs()
+    bar = steps * 2.0 ** -24 * pr.abs().max().item() + 2.0 ** -18 * (pr - p0.double()).abs() + 1e-30
+    assert (err <= bar).all(), "adam p from a random start: %.2f times the bar" % (err / bar).max().item()
 
 
 def test_nms_top1_decode(F):

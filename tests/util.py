@@ -337,3 +337,21 @@ def kernels_run(F):
             names.append(nm.value.decode())
     finally:
         L.pdf_debug_kernel_timing(0)
+
+
+# ----------------------------------------------------------------------------------------------
+def adam_float64(p0, grads, corrs, lr, b1, b2, eps, grad_scale=1.0):
+    """Textbook Adam in float64 on exactly the float32 inputs a sequence of pdf_adam_step calls sees: lr, b1, b2, eps and grad_scale rounded to
+    float32 (1 - b1 and 1 - b2 are then exact in both precisions), grads[t] the float32 gradient of call t and corrs[t] its float32
+    [1 - b1^t, 1 - b2^t] exactly as uploaded.  m and v start at 0.  -> (p, m, v) in float64."""
+    lr, b1, b2, eps, grad_scale = (float(np.float32(a)) for a in (lr, b1, b2, eps, grad_scale))
+    p = p0.double().clone()
+    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    for g, c in zip(grads, corrs):
+        assert g.dtype == torch.float32 and c.dtype == torch.float32
+        g = g.double() * grad_scale
+        bc1, bc2 = c.double().tolist()
+        m = b1 * m + (1 - b1) * g
+        v = b2 * v + (1 - b2) * g * g
+        p = p - (lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + eps)
+    return p, m, v
