@@ -550,6 +550,37 @@ int pdf_mesh_cloud_loss(const float* verts, const long long* faces, const float*
 int pdf_penetration_loss(const float* verts, const long long* faces, const float* valid, int B, int n, int Fc,
                          float* loss, int* count, float* grad_self, float* grad_other,
                          int* inside, int* tri, float* bary, float* closest, void* stream);
+/* Differentiable soft-silhouette loss (csrc/silhouette.hip).  Row (b, h): the triangles of hand h of sample b under that sample's pinhole
+ * camera, each a sigmoid of its signed squared screen distance, aggregated as a product into a soft silhouette S and compared with the
+ * hand's mask by a soft IoU; and the gradient of that loss with respect to the hand's vertices.  No z-buffer, no coverage decision.
+ * verts [B,2,n,3] f32 camera-space metres (left, right); faces [2,Fc,3] int64, the tensor pdf_render_hands takes (an index outside [0, n) is
+ * clamped); K [B,3,3] f32; mask [B,2,H,W] f32 in [0, 1], indexed like verts (left, right); weight [B,2,H,W] f32 >= 0 or NULL (1 everywhere);
+ * valid [B,2] f32 or NULL; table [2,n,M] int32: the faces (0 .. Fc-1 of that hand, ascending) incident to each vertex, padded with -1
+ * (needed for grad only); sigma > 0 in px^2; z_near > 0.  fp32 on the device unless stated.
+ *   Screen     u = K00 X / Z + K02, v = K11 Y / Z + K12; pixel (row i, column j) is sampled at (j + 0.5, i + 0.5): pdf_render_hands's.
+ *   Skipped    whole: a face whose hand has valid == 0; with a vertex at Z < z_near (or not a number); with a screen coordinate that is not
+ *              finite; whose doubled screen area A2 = (x1-x0)(y2-y0) - (x2-x0)(y1-y0) (products rounded separately) is exactly 0.
+ *   Inclusion  face f counts at pixel p iff p's centre lies in f's screen bounding box grown by rho on every side (borders included),
+ *              rho^2 = 16 sigma: a face at its inclusion border contributes at most sigmoid(-16) = 1.1e-7.  The kernels' tiles only prune.
+ *   Per face   d^2 = the squared distance from p to the triangle's boundary: the minimum over the edges 0->1, 1->2, 2->0 (the first of
+ *   and pixel  equals) of |p - (a + t (b - a))|^2, t clamped to [0, 1]; inside: all three edge functions times sign(A2) are >= 0;
+ *              x = +- d^2 / sigma (+ inside); l = log(1 - sigmoid(x)): -(x + log1pf(expf(-x))) for x >= 0, -log1pf(expf(x)) for x < 0.
+ *   Per pixel  T = exp(sum of l over the included faces, in ascending face order), S = 1 - T; T is exactly 1 where no face is included.
+ *   Per row    I = sum w S M, U = sum w (S + M - S M), both in double, in a fixed order (per 16 x 16 tile, then the tiles ascending);
+ *              loss = 1 - I / (U + 1e-6).  A row whose hand is not valid: loss 0, T 1, gradient 0 (sums stay (0, sum w M)).
+ *   Gradient   d loss / d S_p = w_p (-M_p / (U + e) + I (1 - M_p) / (U + e)^2); d S / d x_f = T sigmoid(x_f) (no division by 1 - p_f);
+ *              for the nearest edge a -> b with closest point q: d d^2 / d a = -2 (1 - t)(p - q), d d^2 / d b = -2 t (p - q), clamped or
+ *              not; the third corner gets 0; the pinhole Jacobian maps (du, dv) to (X, Y, Z).  The inclusion set is held constant.  Per
+ *              face the pixels are added per lane of a wave and by a butterfly, per vertex the faces of `table` in ascending order.  A
+ *              vertex that is in no face, or only in skipped ones, gets exactly 0.
+ *   loss  [B,2] f32;  sums [B,2,2] f32: (I, U);  trans [B,2,H,W] f32: T;  grad [B,2,n,3] f32 or NULL: d loss[b,h] / d verts[b,h]
+ * scratch: 8 B n + 8 B ceil(W/16) ceil(H/16) + 4 B + 12 B Fc floats, 16-byte aligned; overwritten by every call.
+ * 1 <= n <= 1024, 1 <= Fc <= 2048, 1 <= H, W <= 2048, 1 <= M <= 32 (pass 1 without a table), B <= 65535, the pointers above not NULL, table
+ * not NULL with grad, else PDF_E_BADARG with nothing launched; B <= 0 returns 0.  No atomics: two runs are bit-identical and a row depends
+ * only on its own hand, camera, mask and weight. */
+int pdf_silhouette_loss(const float* verts, const long long* faces, const float* K, const float* mask, const float* weight,
+                        const float* valid, const int* table, int B, int n, int Fc, int M, int H, int W, float sigma, float z_near,
+                        float* scratch, float* loss, float* sums, float* trans, float* grad, void* stream);
 
 /* ---- hand renderer (csrc/render.hip) ------------------------------------------------------------ */
 /* Forward-only z-buffered rasteriser of both hands of every sample under that sample's pinhole camera (the reference's pytorch3d

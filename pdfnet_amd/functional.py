@@ -2721,6 +2721,87 @@ def render_hands(verts, faces, K, size, valid=None, colour=None, table=None, amb
     return tuple(x for x in (face, depth, bary, rgb) if x is not None)
 
 
+class _SilhouetteLoss(torch.autograd.Function):
+    """loss [..., 2] of `silhouette_loss`; the gradient with respect to verts comes out of the forward call when verts needs it."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, K, mask, weight, valid, sigma, table, z_near, fields, want_grad):
+        v, f, k = verts.detach().float().contiguous(), faces.detach().long().contiguous(), K.detach().float().contiguous()
+        if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
+            raise ValueError("pdfnet_amd: silhouette_loss wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
+        lead, n, Fc = v.shape[:-3], v.shape[-2], f.shape[1]
+        if k.shape != lead + (3, 3):
+            raise ValueError("pdfnet_amd: silhouette_loss wants K %s for verts %s, got %s" % (tuple(lead) + (3, 3), tuple(v.shape), tuple(k.shape)))
+        m = mask.detach().float().contiguous()
+        if m.dim() != len(lead) + 3 or m.shape[:-2] != lead + (2,):
+            raise ValueError("pdfnet_amd: silhouette_loss wants mask %s + (H, W) for verts %s, got %s" % (tuple(lead) + (2,), tuple(v.shape), tuple(m.shape)))
+        H, W = m.shape[-2:]
+        if not (1 <= n <= 1024 and 1 <= Fc <= 2048 and 1 <= H <= 2048 and 1 <= W <= 2048):
+            raise ValueError("pdfnet_amd: silhouette_loss takes 1 to 1024 vertices and 1 to 2048 faces per hand and masks of 1 to 2048 pixels a side, "
+                             "got n = %d, Fc = %d, size = (%d, %d)" % (n, Fc, H, W))
+        if not sigma > 0 or not sigma < float('inf'):
+            raise ValueError("pdfnet_amd: silhouette_loss wants a finite sigma > 0 (px^2), got %r" % (sigma,))
+        if not z_near > 0:
+            raise ValueError("pdfnet_amd: silhouette_loss wants z_near > 0, got %r" % (z_near,))
+        B = v.numel() // (2 * n * 3)
+        if B > 65535:
+            raise ValueError("pdfnet_amd: silhouette_loss takes at most 65535 samples a call, got %d" % B)
+        wt = va = None
+        if weight is not None:
+            wt = weight.detach().float().contiguous()
+            if wt.shape != m.shape:
+                raise ValueError("pdfnet_amd: silhouette_loss wants weight %s, got %s" % (tuple(m.shape), tuple(wt.shape)))
+        if valid is not None:
+            va = valid.detach().float().contiguous()
+            if va.shape != lead + (2,):
+                raise ValueError("pdfnet_amd: silhouette_loss wants valid %s, got %s" % (tuple(lead) + (2,), tuple(va.shape)))
+        M = 1
+        if want_grad:
+            if table is None:
+                table = vertex_face_table(f, n)
+            table = table.detach().int().contiguous()
+            if table.dim() != 3 or table.shape[:2] != (2, n) or not 1 <= table.shape[2] <= RENDER_MAX_DEGREE:
+                raise ValueError("pdfnet_amd: silhouette_loss wants table [2, %d, 1..%d] (vertex_face_table), got %s" % (n, RENDER_MAX_DEGREE, tuple(table.shape)))
+            M = table.shape[2]
+        else:
+            table = None
+        hip.require_gpu(verts, faces, K, mask, weight, valid, table)
+        dev = v.device
+        loss = torch.empty(lead + (2,), dtype=torch.float32, device=dev)
+        sums = torch.empty(lead + (2, 2), dtype=torch.float32, device=dev)
+        trans = torch.empty_like(m)
+        grad = torch.empty_like(v) if want_grad else None
+        tiles = ((W + 15) // 16) * ((H + 15) // 16)
+        scratch = torch.empty(max(B, 1) * (8 * n + 8 * tiles + 4 + 12 * Fc), dtype=torch.float32, device=dev)
+        _L().pdf_silhouette_loss(ptr(v), ptr(f), ptr(k), ptr(m), ptr(wt), ptr(va), ptr(table), B, n, Fc, M, H, W, float(sigma), float(z_near),
+                                 ptr(scratch), ptr(loss), ptr(sums), ptr(trans), ptr(grad), stream())
+        ctx.grad, ctx.dtype = grad, verts.dtype
+        extra = (sums, 1 - trans) if fields else ()
+        ctx.mark_non_differentiable(*extra)
+        return (loss,) + extra
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *unused):
+        return (g[..., None, None] * ctx.grad).to(ctx.dtype), None, None, None, None, None, None, None, None, None, None
+
+
+def silhouette_loss(verts, faces, K, mask, weight=None, valid=None, sigma=1.0, table=None, z_near=0.01, return_fields=False):
+    """verts [..., 2, n, 3] camera-space metres (left, right hand), faces [2, Fc, 3] int64 (the loss module's `faces_pair`), K [..., 3, 3] as
+    `render_hands` takes them; mask [..., 2, H, W] in [0, 1], indexed like verts (left, right); weight [..., 2, H, W] >= 0 or None (1);
+    valid [..., 2] or None -> loss [..., 2], unitless in [0, 1]: per hand 1 - I / (U + 1e-6), the soft intersection over union of the
+    mask M with the hand's soft silhouette S = 1 - prod over its triangles of (1 - sigmoid(+-d^2 / sigma)), d the distance in pixels from the
+    pixel centre to the triangle's boundary (+ inside), I = sum w S M, U = sum w (S + M - S M).  sigma (px^2) sets the width of the edge; a
+    triangle counts at the pixels within sqrt(16 sigma) of its bounding box.  There is no z-buffer: each hand is drawn alone.  A hand with
+    valid 0 gives loss 0.  Differentiable once, with respect to `verts` only (not K, mask, weight or sigma); the gradient comes out of the
+    forward call, backward is one multiplication.  table: `vertex_face_table(faces, n)`, which the gradient is gathered over; built here (on
+    the host) when it is needed and missing.  return_fields: (loss, sums [..., 2, 2]: (I, U), silhouette [..., 2, H, W]: S).  The contract is
+    `pdf_silhouette_loss`'s in pdfnet_hip.h.  n <= 1024, Fc <= 2048, H, W <= 2048.  Deterministic."""
+    out = _SilhouetteLoss.apply(verts, faces, K, mask, weight, valid, float(sigma), table, float(z_near), bool(return_fields),
+                                torch.is_grad_enabled() and verts.requires_grad)
+    return out if return_fields else out[0]
+
+
 def render_compare(face_pred, face_gt, depth_pred, Fc, sensor=None):
     """Two face maps of `render_hands` [..., H, W] int32 (prediction, ground truth), the prediction's depth map and optionally a sensor depth map
     [..., H, W] (metres, <= 0 = no measurement) -> (iou int32 [..., 2, 2]: per hand (left, right) the number of pixels where it is the visible

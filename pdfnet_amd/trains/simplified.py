@@ -115,6 +115,28 @@ def penetration_term(vp, root, ind, batch, faces, input_res, down_ratio=4):
     return 1e6 * F.penetration_loss(verts, faces, valid=valid).sum(1)
 
 
+def silhouette_term(vp, root, ind, batch, faces, input_res, down_ratio=4, sigma=1.0, down=2, table=None):
+    """The soft-silhouette training term -> [B], unitless in 0 .. 2: the sum over the valid hands of `F.silhouette_loss` (one minus the soft
+    intersection over union of the hand's segmentation mask with the soft silhouette of its predicted mesh, each hand drawn alone).
+    vp, root, ind, faces and the absolute vertices are `cloud_term`'s; batch: `mask` [B, 2, R, R] in (right, left) order, `valid` [B, 2],
+    `K_new`.  The masks are flipped to (left, right) and average-pooled by the integer `down`; the camera's rows 0 and 1 are divided by it,
+    which is exact under the pixel-centre convention (pixel j covers [j, j + 1)).  Where the OTHER hand's mask is set that hand is the
+    visible surface and this hand's coverage is unknown: the pixel's weight is 1 - the other hand's mask, so it is not judged.
+    sigma: px^2 of the pooled image; table: `F.vertex_face_table(faces, 778)`.  Differentiable in vp and root."""
+    if 'mask' not in batch:
+        raise KeyError("CtdetLoss: silhouette_weight > 0 needs batch['mask'], the hands' segmentation masks [B, 2, R, R] in (right, left) "
+                       "order (interhand.py H2O entries)")
+    verts, valid = _abs_verts(vp, root, ind, batch, input_res, down_ratio)
+    mask = batch['mask'].flip(1).float()
+    down = int(down)
+    if down > 1:
+        mask = torch.nn.functional.avg_pool2d(mask, down)
+    K = batch['K_new'].float().clone()
+    K[:, :2] /= down
+    loss = F.silhouette_loss(verts, faces, K, mask, weight=1 - mask.flip(1), valid=valid, sigma=sigma, table=table)
+    return (valid * loss).sum(1)
+
+
 FORK_DENSE_LOSS = os.environ.get("PDFNET_FORK_DENSE_LOSS", "1") != "0"
 
 
@@ -124,7 +146,10 @@ class CtdetLoss(nn.Module):
     stats['cloud_loss']), mesh_cloud_weight (0; > 0: likewise mesh_cloud_weight * `mesh_cloud_term`, stats['mesh_cloud_loss']), cloud_trim (0.03 m,
     both terms), cloud_margin (0.002 m: how far in front of a vertex an occluder must lie to hide it), penetration_weight (0: the inter-hand
     penetration term `penetration_term` is neither computed nor launched; > 0: train mode adds penetration_weight * penetration_loss, after
-    the two cloud terms, and reports stats['penetration_loss']; it needs no batch['cloud']).
+    the two cloud terms, and reports stats['penetration_loss']; it needs no batch['cloud']), silhouette_weight (0: the soft-silhouette term
+    `silhouette_term` is neither computed nor launched; > 0: train mode adds silhouette_weight * silhouette_loss, after the penetration term,
+    and reports stats['silhouette_loss']; it reads batch['mask']), silhouette_sigma (1.0 px^2 of the pooled mask: the width of the soft edge),
+    silhouette_down (2: the masks are average-pooled by this integer before they are compared).
     `consts`: {'full_regressor_left/right' [21,778], 'faces_left/right' [1538,3] int64}."""
 
     def __init__(self, opt, consts):
@@ -137,6 +162,7 @@ class CtdetLoss(nn.Module):
         self.register_buffer('bone_c', torch.tensor([b[1] for b in _BONES]), persistent=False)
         self.register_buffer('_hand_scales', torch.tensor([1.0, 1.0, 1000.0, 1000.0, 1000.0, 1.0, 1.0]).view(7, 1, 1), persistent=False)
         self._coef_cache = {}
+        self._sil_table = None                               # F.vertex_face_table(faces_pair), built on the first step with silhouette_weight > 0
 
     def forward(self, result, paramsDict, handDictList, otherInfo, batch, mode, epoch):
         test = mode in ('val', 'test')
@@ -185,6 +211,16 @@ class CtdetLoss(nn.Module):
                                   getattr(self.opt, 'down_ratio', 4))
             loss = loss + pw * pl
             stats['penetration_loss'] = pl
+            stats['loss'] = loss
+        sw = getattr(self.opt, 'silhouette_weight', 0)
+        if sw > 0:                                           # the image plane: each hand's soft silhouette against its segmentation mask
+            if self._sil_table is None or self._sil_table.device != self.faces_pair.device:
+                self._sil_table = F.vertex_face_table(self.faces_pair, 778)
+            sl = silhouette_term(_pair(result['verts3d']), _pair(paramsDict['root']), ind, batch, self.faces_pair, int(self.opt.size_train[0]),
+                                 getattr(self.opt, 'down_ratio', 4), getattr(self.opt, 'silhouette_sigma', 1.0),
+                                 getattr(self.opt, 'silhouette_down', 2), self._sil_table)
+            loss = loss + sw * sl
+            stats['silhouette_loss'] = sl
             stats['loss'] = loss
         return loss, stats, None, None
 
