@@ -21,7 +21,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_internal.h"), os.path.join(CSRC, "svd3.h"), os.path.join(CSRC, "icp_common.h"), os.path.join(INCLUDE, "pdfnet_hip.h")]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_internal.h"), os.path.join(CSRC, "svd3.h"), os.path.join(CSRC, "mesh_geom.h"), os.path.join(INCLUDE, "pdfnet_hip.h")]
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

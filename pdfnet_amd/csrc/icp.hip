@@ -16,9 +16,8 @@
 //   the iterations and out_verts is exactly the fp32 rounding of R v + t.
 // No atomics, no global scratch: two runs are bit-identical and a row does not depend on the other rows of the batch.
 // The same association feeds cloud_mesh_loss_kernel at the end of this file: the residual as a loss, with its gradient (pdf_cloud_mesh_loss).
-#include "common.h"
-#include "svd3.h"
-#include "icp_common.h"                                         // ICP_T .. ICP_MAXP, icp_det2, icp_dot3, icp_dot, icp_block_sum (shared with meshcloud.hip); IcpShared and icp_walk (shared with penetration.hip)
+#include "svd3.h"                                               // met_svd_3x3
+#include "mesh_geom.h"
 
 #define ICP_MAXIT 64
 
@@ -35,9 +34,7 @@ __device__ __forceinline__ int icp_facing(IcpShared& s, int Fc) {
             ax = s.vx[f.x]; ay = s.vy[f.x]; az = s.vz[f.x];
             bx = s.vx[f.y]; by = s.vy[f.y]; bz = s.vz[f.y];
             cx = s.vx[f.z]; cy = s.vy[f.z]; cz = s.vz[f.z];
-            const float e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
-            const float nx = icp_det2(e1y, e2z, e1z, e2y), ny = icp_det2(e1z, e2x, e1x, e2z), nz = icp_det2(e1x, e2y, e1y, e2x);
-            keep = icp_dot3(nx, ax + bx + cx, ny, ay + by + cy, nz, az + bz + cz) < 0.f;
+            keep = geo_faces_camera(ax, ay, az, bx, by, bz, cx, cy, cz);
         }
         const unsigned long long mask = __ballot(keep);
         if (lane == 0) s.wave_n[wave] = __popcll(mask);
@@ -49,7 +46,7 @@ __device__ __forceinline__ int icp_facing(IcpShared& s, int Fc) {
             if (w < wave) off += c;
             total += c;
         }
-        if (keep) {                                            // off < total <= base + ICP_T, at most Fc <= ICP_MAXF
+        if (keep) {                                            // off < total <= base + ICP_T, at most Fc <= HAND_MAXF
             s.ca[off] = make_float4(ax, ay, az, __int_as_float(g));
             s.cb[off] = make_float4(bx, by, bz, 0.f);
             s.cc[off] = make_float4(cx, cy, cz, 0.f);
@@ -124,15 +121,7 @@ __global__ __launch_bounds__(ICP_T) void mesh_icp_kernel(const float* __restrict
         return;
     }
     if (t < n) { s.vx[t] = vp[0]; s.vy[t] = vp[1]; s.vz[t] = vp[2]; }
-    const long long* fo = faces + (long)h * Fc * 3;
-    for (int g = t; g < Fc; g += ICP_T) {
-        ushort4 f;                                             // an index outside [0, n) is clamped: it must not leave the staged planes
-        f.x = (unsigned short)min(max(fo[3 * g + 0], 0LL), (long long)(n - 1));
-        f.y = (unsigned short)min(max(fo[3 * g + 1], 0LL), (long long)(n - 1));
-        f.z = (unsigned short)min(max(fo[3 * g + 2], 0LL), (long long)(n - 1));
-        f.w = 0;
-        s.tri[g] = f;
-    }
+    geo_stage_faces(faces + (long)h * Fc * 3, Fc, n, s.tri);
     if (t < 12) s.xf[t] = t < 9 && t % 4 == 0 ? 1.0 : 0.0;
     if (t == 0) s.stop = 0;
     __syncthreads();
@@ -185,7 +174,7 @@ PDF_API int pdf_mesh_icp(const float* verts, const long long* faces, const float
                          void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (n < 1 || n > ICP_MAXN || Fc < 1 || Fc > ICP_MAXF || P < 1 || P > ICP_MAXP || iters < 0 || iters > ICP_MAXIT || !(trim > 0.f) ||
+    if (n < 1 || n > HAND_MAXN || Fc < 1 || Fc > HAND_MAXF || P < 1 || P > HAND_MAXP || iters < 0 || iters > ICP_MAXIT || !(trim > 0.f) ||
         !(trim <= 3.0e38f) || verts == nullptr || faces == nullptr || cloud == nullptr || rms == nullptr || inliers == nullptr)
         return PDF_E_BADARG;
     hipLaunchKernelGGL(mesh_icp_kernel, dim3(2 * B), dim3(ICP_T), 0, s, verts, faces, cloud, valid, n, Fc, P, iters, trim, rigid, out_verts, R, t,
@@ -198,10 +187,8 @@ PDF_API int pdf_mesh_icp(const float* verts, const long long* faces, const float
 // The association of mesh_icp_kernel with iters = 0 -- icp_facing and icp_walk, shared -- then loss = mean |p - q|^2 over the inliers and its
 // gradient with respect to the vertices: corner k of an inlier's triangle receives -(2/m) w_k (p - q) (the envelope theorem: q is the minimiser
 // over the triangle, so only the explicit dependence of q = wa a + wb b + wc c on the corners counts).
-// Gather without atomics: once the walk is over the corner list is dead, and behind the block sum's barriers lane t writes point t's record
-// over its head: s.ca[t] = (wa, wb, wc, corner indices 0 and 1 as 16-bit halves), s.cb[t] = (-(2/m) (p - q), corner index 2); a point that is
-// no inlier writes the index 0xffff, which is no vertex.  Lane t < n then reads the P records front to back, every lane the same record (two
-// broadcast 16-byte reads), and adds those that name vertex t, in double, in ascending point order.
+// The gather is without atomics: geo_corner_gather over the P records of the row's points, each carrying -(2/m) (p - q), behind the block
+// sum's barriers; lane t < n gets the sum for vertex t, added in double in ascending point order.
 __global__ __launch_bounds__(ICP_T) void cloud_mesh_loss_kernel(const float* __restrict__ verts, const long long* __restrict__ faces,
                                                                 const float* __restrict__ cloud, const float* __restrict__ valid, int n, int Fc,
                                                                 int P, float trim, float* __restrict__ loss, int* __restrict__ inliers,
@@ -226,15 +213,7 @@ __global__ __launch_bounds__(ICP_T) void cloud_mesh_loss_kernel(const float* __r
         return;
     }
     if (t < n) { s.vx[t] = vp[0]; s.vy[t] = vp[1]; s.vz[t] = vp[2]; }
-    const long long* fo = faces + (long)h * Fc * 3;
-    for (int g = t; g < Fc; g += ICP_T) {
-        ushort4 f;                                             // an index outside [0, n) is clamped: it must not leave the staged planes
-        f.x = (unsigned short)min(max(fo[3 * g + 0], 0LL), (long long)(n - 1));
-        f.y = (unsigned short)min(max(fo[3 * g + 1], 0LL), (long long)(n - 1));
-        f.z = (unsigned short)min(max(fo[3 * g + 2], 0LL), (long long)(n - 1));
-        f.w = 0;
-        s.tri[g] = f;
-    }
+    geo_stage_faces(faces + (long)h * Fc * 3, Fc, n, s.tri);
     __syncthreads();
 
     const int count = icp_facing(s, Fc);                       // (ends in a barrier)
@@ -256,25 +235,12 @@ __global__ __launch_bounds__(ICP_T) void cloud_mesh_loss_kernel(const float* __r
         if (tri != nullptr) tri[row * P + t] = hit ? face : -1;
     }
     if (grad == nullptr) return;                               // block-uniform
-    if (t < P) {
-        const float sc = in ? (float)(-2.0 / m) : 0.f;
-        ushort4 f = make_ushort4(0xffff, 0xffff, 0xffff, 0);
-        if (in) f = s.tri[face];                               // face < Fc: it came out of the list
-        s.ca[t] = make_float4(wa, wb, wc, __int_as_float((int)f.x | ((int)f.y << 16)));
-        s.cb[t] = make_float4(in ? sc * (px - qx) : 0.f, in ? sc * (py - qy) : 0.f, in ? sc * (pz - qz) : 0.f, __int_as_float((int)f.z));
-    }
-    __syncthreads();
+    const float sc = in ? (float)(-2.0 / m) : 0.f;
+    const double3 gv = geo_corner_gather(s, wa, wb, wc, in ? sc * (px - qx) : 0.f, in ? sc * (py - qy) : 0.f, in ? sc * (pz - qz) : 0.f,
+                                         in ? face : -1, P, n);
     if (t < n) {
-        double gx = 0.0, gy = 0.0, gz = 0.0;
-        for (int j = 0; j < P; ++j) {
-            const float4 ra = s.ca[j], rb = s.cb[j];
-            const int i01 = __float_as_int(ra.w), i2 = __float_as_int(rb.w);
-            if ((i01 & 0xffff) == t) { gx += (double)(ra.x * rb.x); gy += (double)(ra.x * rb.y); gz += (double)(ra.x * rb.z); }
-            if (((i01 >> 16) & 0xffff) == t) { gx += (double)(ra.y * rb.x); gy += (double)(ra.y * rb.y); gz += (double)(ra.y * rb.z); }
-            if (i2 == t) { gx += (double)(ra.z * rb.x); gy += (double)(ra.z * rb.y); gz += (double)(ra.z * rb.z); }
-        }
         float* g = grad + (row * n + t) * 3;
-        g[0] = (float)gx; g[1] = (float)gy; g[2] = (float)gz;
+        g[0] = (float)gv.x; g[1] = (float)gv.y; g[2] = (float)gv.z;
     }
 }
 
@@ -282,7 +248,7 @@ PDF_API int pdf_cloud_mesh_loss(const float* verts, const long long* faces, cons
                                 float trim, float* loss, int* inliers, float* grad, int* tri, float* closest, float* bary, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (n < 1 || n > ICP_MAXN || Fc < 1 || Fc > ICP_MAXF || P < 1 || P > ICP_MAXP || !(trim > 0.f) || !(trim <= 3.0e38f) || verts == nullptr ||
+    if (n < 1 || n > HAND_MAXN || Fc < 1 || Fc > HAND_MAXF || P < 1 || P > HAND_MAXP || !(trim > 0.f) || !(trim <= 3.0e38f) || verts == nullptr ||
         faces == nullptr || cloud == nullptr || loss == nullptr || inliers == nullptr)
         return PDF_E_BADARG;
     hipLaunchKernelGGL(cloud_mesh_loss_kernel, dim3(2 * B), dim3(ICP_T), 0, s, verts, faces, cloud, valid, n, Fc, P, trim, loss, inliers, grad, tri,

@@ -8,12 +8,12 @@
 //   list of occluders, 48 B an entry: the three corners, and in the spare words the three vertex indices as 16-bit values (0xffff, which is
 //   no vertex, for a triangle of the other hand).  The camera-facing triangles of both hands at the bounds are 2 x 2,048 x 48 B, which does
 //   not fit, so the occluders are streamed in chunks of 1,024 faces: lane t tests face base + t of the own hand, then of the other hand, by
-//   icp_facing's rule and forms; the survivors are compacted in face order by a 64-bit __ballot + popcount prefix per wave and the wave totals
+//   icp_facing's test (geo_faces_camera); the survivors are compacted in face order by a 64-bit __ballot + popcount prefix per wave and the wave totals
 //   through LDS (render_tile_kernel's idiom); behind a barrier every lane walks the list front to back, every lane the same entry: three
 //   broadcast 16-byte reads.  A wave none of whose lanes can still change its answer skips the walk of a chunk.
 //   Occlusion: the ray from the vertex v to the camera at the origin against triangle (a, b, c), with the corners taken relative to the vertex
 //   (a' = a - v, ...): s0 = v . (b' x c'), s1 = v . (c' x a'), s2 = v . (a' x b'), S = s0 + s1 + s2, det = a' . (b' x c').  The cross products
-//   are made of separately rounded products (icp_det2) and the dot products are icp_dot, so each s_k is EXACTLY odd in the exchange of its
+//   are made of separately rounded products (geo_det2) and the dot products are icp_dot, so each s_k is EXACTLY odd in the exchange of its
 //   edge's two corners: evaluating it from the lower to the higher vertex index and negating as needed (render.hip's idiom) gives the bits
 //   that the direct evaluation gives, and the two faces at an edge agree up to sign -- a ray through a shared edge or vertex hits both, a
 //   closed surface has no gap.  Hit: s0, s1, s2 >= 0 and S > 0, or s0, s1, s2 <= 0 and S < 0.  With D = -det (S > 0) or det, A = |S|, the
@@ -23,7 +23,7 @@
 //   value replaces the best, so the lowest point index wins a tie; a point with Z <= 0 is passed over.
 //   Sums: inliers, sum |v - p|^2 and visible vertices as doubles through icp_block_sum, the fixed-order reduction of icp.hip.
 // No atomics, no global scratch: two runs are bit-identical and a row depends only on the two hands of its own sample.
-#include "icp_common.h"
+#include "mesh_geom.h"
 
 #define MC_CHUNK ICP_T                                         // faces set up per pass = the capacity of the occluder list
 #define MC_NOVERT 0xffff
@@ -31,10 +31,10 @@
 struct McShared {                                              // (the small members first: their addresses fit a DS instruction's 16-bit offset)
     double red[ICP_W * 3], sum[3];
     int wave_n[ICP_W];
-    float vx[2][ICP_MAXN], vy[2][ICP_MAXN], vz[2][ICP_MAXN];   // [0]: this row's hand, [1]: the other hand of the sample
-    alignas(16) float px[ICP_MAXP];
-    alignas(16) float py[ICP_MAXP];
-    alignas(16) float pz[ICP_MAXP];
+    float vx[2][HAND_MAXN], vy[2][HAND_MAXN], vz[2][HAND_MAXN];      // [0]: this row's hand, [1]: the other hand of the sample
+    alignas(16) float px[HAND_MAXP];
+    alignas(16) float py[HAND_MAXP];
+    alignas(16) float pz[HAND_MAXP];
     float4 ca[MC_CHUNK], cb[MC_CHUNK], cc[MC_CHUNK];           // corners; ca.w: indices of a and b as 16-bit halves, cb.w: index of c
 };
 
@@ -47,16 +47,12 @@ __device__ __forceinline__ int mc_occluders(McShared& s, const long long* __rest
     bool keep = false;
     int ia = 0, ib = 0, ic = 0;
     float ax = 0.f, ay = 0.f, az = 0.f, bx = 0.f, by = 0.f, bz = 0.f, cx = 0.f, cy = 0.f, cz = 0.f;
-    if (g < Fc) {                                              // an index outside [0, n) is clamped: it must not leave the staged planes
-        ia = (int)min(max(fo[3 * g + 0], 0LL), (long long)(n - 1));
-        ib = (int)min(max(fo[3 * g + 1], 0LL), (long long)(n - 1));
-        ic = (int)min(max(fo[3 * g + 2], 0LL), (long long)(n - 1));
+    if (g < Fc) {
+        ia = geo_index(fo + 3 * g, n); ib = geo_index(fo + 3 * g + 1, n); ic = geo_index(fo + 3 * g + 2, n);
         ax = s.vx[which][ia]; ay = s.vy[which][ia]; az = s.vz[which][ia];
         bx = s.vx[which][ib]; by = s.vy[which][ib]; bz = s.vz[which][ib];
         cx = s.vx[which][ic]; cy = s.vy[which][ic]; cz = s.vz[which][ic];
-        const float e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
-        const float nx = icp_det2(e1y, e2z, e1z, e2y), ny = icp_det2(e1z, e2x, e1x, e2z), nz = icp_det2(e1x, e2y, e1y, e2x);
-        keep = icp_dot3(nx, ax + bx + cx, ny, ay + by + cy, nz, az + bz + cz) < 0.f;
+        keep = geo_faces_camera(ax, ay, az, bx, by, bz, cx, cy, cz);
     }
     const unsigned long long mask = __ballot(keep);
     if (lane == 0) s.wave_n[wave] = __popcll(mask);
@@ -126,10 +122,10 @@ __global__ __launch_bounds__(ICP_T) void mesh_cloud_loss_kernel(const float* __r
                 const float ax = a.x - vx, ay = a.y - vy, az = a.z - vz;
                 const float bx = b.x - vx, by = b.y - vy, bz = b.z - vz;
                 const float cx = c.x - vx, cy = c.y - vy, cz = c.z - vz;
-                const float ux = icp_det2(by, cz, bz, cy), uy = icp_det2(bz, cx, bx, cz), uz = icp_det2(bx, cy, by, cx);      // b' x c'
+                const float ux = geo_det2(by, cz, bz, cy), uy = geo_det2(bz, cx, bx, cz), uz = geo_det2(bx, cy, by, cx);      // b' x c'
                 const float s0 = icp_dot(vx, vy, vz, ux, uy, uz);
-                const float s1 = icp_dot(vx, vy, vz, icp_det2(cy, az, cz, ay), icp_det2(cz, ax, cx, az), icp_det2(cx, ay, cy, ax));
-                const float s2 = icp_dot(vx, vy, vz, icp_det2(ay, bz, az, by), icp_det2(az, bx, ax, bz), icp_det2(ax, by, ay, bx));
+                const float s1 = icp_dot(vx, vy, vz, geo_det2(cy, az, cz, ay), geo_det2(cz, ax, cx, az), geo_det2(cx, ay, cy, ax));
+                const float s2 = icp_dot(vx, vy, vz, geo_det2(ay, bz, az, by), geo_det2(az, bx, ax, bz), geo_det2(ax, by, ay, bx));
                 const float det = icp_dot(ax, ay, az, ux, uy, uz);
                 const float S = s0 + s1 + s2;
                 const bool hit = (s0 >= 0.f && s1 >= 0.f && s2 >= 0.f && S > 0.f) || (s0 <= 0.f && s1 <= 0.f && s2 <= 0.f && S < 0.f);
@@ -180,7 +176,7 @@ PDF_API int pdf_mesh_cloud_loss(const float* verts, const long long* faces, cons
                                 float trim, float margin, float* loss, int* inliers, int* visible, float* grad, int* vis, int* nn, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (n < 1 || n > ICP_MAXN || Fc < 1 || Fc > ICP_MAXF || P < 1 || P > ICP_MAXP || !(trim > 0.f) || !(trim <= 3.0e38f) || !(margin >= 0.f) ||
+    if (n < 1 || n > HAND_MAXN || Fc < 1 || Fc > HAND_MAXF || P < 1 || P > HAND_MAXP || !(trim > 0.f) || !(trim <= 3.0e38f) || !(margin >= 0.f) ||
         !(margin <= 3.0e38f) || verts == nullptr || faces == nullptr || cloud == nullptr || loss == nullptr || inliers == nullptr ||
         visible == nullptr)
         return PDF_E_BADARG;

@@ -3,18 +3,10 @@
 // F-scores.  Like point_dist_sum_kernel (loss.hip): one block of 256 threads per row = (sample, hand), the points of the row staged in LDS as
 // x / y / z planes.  No atomics, every reduction in a fixed order: two runs on the same input are bit-identical.
 #include "common.h"
-#include "svd3.h"                                             // wave_sum_d, met_procrustes_3x3
+#include "svd3.h"                                             // met_procrustes_3x3
+#include "mesh_geom.h"                                        // HAND_MAXN, HAND_MAXF, geo_stage_planes, geo_stage_faces, geo_solid_angle
 
 #define MET_T 256
-#define MET_MAXN 1024
-
-// row [n][3] (global) -> planes x, y, z [n] (LDS); consecutive lanes read consecutive floats
-__device__ __forceinline__ void met_stage(const float* __restrict__ row, int n, float* x, float* y, float* z) {
-    for (int e = threadIdx.x; e < 3 * n; e += MET_T) {
-        const int i = e / 3, k = e - 3 * i;
-        (k == 0 ? x : k == 1 ? y : z)[i] = row[e];
-    }
-}
 
 // v[0..K) summed over the block, every thread gets the result; sm [4 * K].  Wave partials by the xor butterfly, then (w0 + w1) + (w2 + w3).
 template <int K>
@@ -34,12 +26,12 @@ __device__ __forceinline__ void block_sum_d(double* v, double* sm) {
 // of aligned coordinates ~100x their size, and the double rate is not what bounds 1,000 points per block.
 __global__ __launch_bounds__(MET_T) void procrustes_dist_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int n,
                                                                 float* __restrict__ sum, float* __restrict__ dist, float* __restrict__ aligned) {
-    __shared__ float gx[MET_MAXN], gy[MET_MAXN], gz[MET_MAXN], px[MET_MAXN], py[MET_MAXN], pz[MET_MAXN];
+    __shared__ float gx[HAND_MAXN], gy[HAND_MAXN], gz[HAND_MAXN], px[HAND_MAXN], py[HAND_MAXN], pz[HAND_MAXN];
     __shared__ double red[4 * 11];
     __shared__ double trafo[12];                               // s * s1 / s2 * R (row-major), then t1
     const long row = blockIdx.x;
-    met_stage(gt + row * n * 3, n, gx, gy, gz);
-    met_stage(pred + row * n * 3, n, px, py, pz);
+    geo_stage_planes(gt + row * n * 3, n, gx, gy, gz);
+    geo_stage_planes(pred + row * n * 3, n, px, py, pz);
     __syncthreads();
     // pass 1: the means t1 (gt), t2 (pred)
     double m[6] = {0, 0, 0, 0, 0, 0};
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(MET_T) void procrustes_dist_kernel(const float* __r
 PDF_API int pdf_procrustes_dist(const float* pred, const float* gt, int rows, int n, float* sum, float* dist, float* aligned, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (rows <= 0 || n <= 0) return 0;
-    if (n > MET_MAXN) return PDF_E_BADARG;
+    if (n > HAND_MAXN) return PDF_E_BADARG;
     hipLaunchKernelGGL(procrustes_dist_kernel, dim3(rows), dim3(MET_T), 0, s, pred, gt, n, sum, dist, aligned);
     PDF_LAUNCH_CHECK();
     return 0;
@@ -136,14 +128,14 @@ __device__ __forceinline__ void met_nn_scan(const float* sx, const float* sy, co
 
 __global__ __launch_bounds__(MET_T) void mesh_nn_counts_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int n, MetThr thr, int T,
                                                                int* __restrict__ counts, float* __restrict__ d_gt, float* __restrict__ d_pred) {
-    __shared__ float4 planes[6][MET_MAXN / 4];                 // (float4: the scan reads four points per 16-byte access)
+    __shared__ float4 planes[6][HAND_MAXN / 4];                // (float4: the scan reads four points per 16-byte access)
     __shared__ int red[4][2 * MET_MAXT];
     float *gx = reinterpret_cast<float*>(planes[0]), *gy = reinterpret_cast<float*>(planes[1]), *gz = reinterpret_cast<float*>(planes[2]);
     float *px = reinterpret_cast<float*>(planes[3]), *py = reinterpret_cast<float*>(planes[4]), *pz = reinterpret_cast<float*>(planes[5]);
     const long row = blockIdx.x;
-    const int n4 = (n + 3) & ~3;                               // <= MET_MAXN, which is a multiple of four
-    met_stage(gt + row * n * 3, n, gx, gy, gz);
-    met_stage(pred + row * n * 3, n, px, py, pz);
+    const int n4 = (n + 3) & ~3;                               // <= HAND_MAXN, which is a multiple of four
+    geo_stage_planes(gt + row * n * 3, n, gx, gy, gz);
+    geo_stage_planes(pred + row * n * 3, n, px, py, pz);
     if (threadIdx.x < n4 - n) {
         const int i = n + threadIdx.x;
         gx[i] = gy[i] = gz[i] = px[i] = py[i] = pz[i] = MET_FAR;
@@ -168,7 +160,7 @@ PDF_API int pdf_mesh_nn_counts(const float* pred, const float* gt, int rows, int
                                void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (rows <= 0 || n <= 0) return 0;
-    if (n > MET_MAXN || T < 1 || T > MET_MAXT || thr == nullptr) return PDF_E_BADARG;
+    if (n > HAND_MAXN || T < 1 || T > MET_MAXT || thr == nullptr) return PDF_E_BADARG;
     MetThr th = {{0.f, 0.f, 0.f, 0.f}};
     for (int t = 0; t < T; ++t) th.t[t] = thr[t];              // host array: travels in the kernel arguments
     hipLaunchKernelGGL(mesh_nn_counts_kernel, dim3(rows), dim3(MET_T), 0, s, pred, gt, n, th, T, counts, d_gt, d_pred);
@@ -187,15 +179,8 @@ PDF_API int pdf_mesh_nn_counts(const float* pred, const float* gt, int rows, int
 // A triangle collapsed to a point has a.(b x c) = 0 and n = 0 exactly: it adds atan2(0, den >= +0) = 0 and the distance to that point.
 // Nothing is divided by a length that can be zero, so finite coordinates (|x| < 1e6: the cubes stay finite) give finite output.
 #define PEN_T 1024
-#define PEN_MAXF 2048
 #define PEN_TINY 1e-37f
 
-// p q - r s from separately rounded products (no fma): a cross product built from it is exactly zero for equal vectors and exactly negated
-// when the two change places
-__device__ __forceinline__ float pen_det2(float p, float q, float r, float s) {
-#pragma clang fp contract(off)
-    return p * q - r * s;
-}
 __device__ __forceinline__ float pen_seg_d2(float px, float py, float pz, float ex, float ey, float ez) {
     // squared distance from the origin to the segment p + t e, t in [0, 1]
     const float ee = ex * ex + ey * ey + ez * ez, pe = px * ex + py * ey + pz * ez;
@@ -207,26 +192,15 @@ __device__ __forceinline__ float pen_seg_d2(float px, float py, float pz, float 
 __global__ __launch_bounds__(PEN_T) void mesh_penetration_kernel(const float* __restrict__ verts, const long long* __restrict__ faces, int n, int Fc,
                                                                  float* __restrict__ wind, float* __restrict__ dist, int* __restrict__ count,
                                                                  float* __restrict__ depth, float* __restrict__ gap) {
-    __shared__ float ox[MET_MAXN], oy[MET_MAXN], oz[MET_MAXN];
-    __shared__ ushort4 tri[PEN_MAXF];
+    __shared__ float ox[HAND_MAXN], oy[HAND_MAXN], oz[HAND_MAXN];
+    __shared__ ushort4 tri[HAND_MAXF];
     __shared__ int red_c[PEN_T / 64];
     __shared__ float red_d[PEN_T / 64], red_g[PEN_T / 64];
     const long row = blockIdx.x;
     const int h = (int)(row & 1);
     const float* other = verts + (row ^ 1) * n * 3;            // rows 2b, 2b + 1 are the two hands of sample b
-    for (int e = threadIdx.x; e < 3 * n; e += PEN_T) {
-        const int i = e / 3, k = e - 3 * i;
-        (k == 0 ? ox : k == 1 ? oy : oz)[i] = other[e];
-    }
-    const long long* fo = faces + (long)(1 - h) * Fc * 3;
-    for (int t = threadIdx.x; t < Fc; t += PEN_T) {
-        ushort4 f;                                             // an index outside [0, n) is clamped: it must not leave the staged planes
-        f.x = (unsigned short)min(max(fo[3 * t + 0], 0LL), (long long)(n - 1));
-        f.y = (unsigned short)min(max(fo[3 * t + 1], 0LL), (long long)(n - 1));
-        f.z = (unsigned short)min(max(fo[3 * t + 2], 0LL), (long long)(n - 1));
-        f.w = 0;
-        tri[t] = f;
-    }
+    geo_stage_planes(other, n, ox, oy, oz);
+    geo_stage_faces(faces + (long)(1 - h) * Fc * 3, Fc, n, tri);
     __syncthreads();
     int cnt = 0;
     float dep = 0.f, gp = 3.0e38f;
@@ -240,11 +214,8 @@ __global__ __launch_bounds__(PEN_T) void mesh_penetration_kernel(const float* __
             const float ax = ox[f.x] - x, ay = oy[f.x] - y, az = oz[f.x] - z;
             const float bx = ox[f.y] - x, by = oy[f.y] - y, bz = oz[f.y] - z;
             const float cx = ox[f.z] - x, cy = oy[f.z] - y, cz = oz[f.z] - z;
-            const float la = sqrtf(ax * ax + ay * ay + az * az), lb = sqrtf(bx * bx + by * by + bz * bz), lc = sqrtf(cx * cx + cy * cy + cz * cz);
-            const float ab = ax * bx + ay * by + az * bz, bc = bx * cx + by * cy + bz * cz, ca = cx * ax + cy * ay + cz * az;
-            const float ux = pen_det2(by, cz, bz, cy), uy = pen_det2(bz, cx, bx, cz), uz = pen_det2(bx, cy, by, cx);      // b x c
-            const float det = ax * ux + ay * uy + az * uz;
-            const float den = la * lb * lc + ab * lc + bc * la + ca * lb;
+            float det, den;
+            geo_solid_angle(ax, ay, az, bx, by, bz, cx, cy, cz, det, den);      // (shared with penetration_loss_kernel: its `inside` is this wind > 0.5)
             omega += (double)atan2f(det, den);
             // edges e1 = b - a, e2 = c - a; d1 .. d6 of the region test: e1.(-a), e2.(-a), e1.(-b), e2.(-b), e1.(-c), e2.(-c)
             const float e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
@@ -287,7 +258,7 @@ PDF_API int pdf_mesh_penetration(const float* verts, const long long* faces, int
                                  float* depth, float* gap, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (n < 1 || n > MET_MAXN || Fc < 1 || Fc > PEN_MAXF || verts == nullptr || faces == nullptr || count == nullptr || depth == nullptr || gap == nullptr)
+    if (n < 1 || n > HAND_MAXN || Fc < 1 || Fc > HAND_MAXF || verts == nullptr || faces == nullptr || count == nullptr || depth == nullptr || gap == nullptr)
         return PDF_E_BADARG;
     hipLaunchKernelGGL(mesh_penetration_kernel, dim3(2 * B), dim3(PEN_T), 0, s, verts, faces, n, Fc, wind, dist, count, depth, gap);
     PDF_LAUNCH_CHECK();

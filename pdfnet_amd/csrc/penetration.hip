@@ -2,45 +2,19 @@
 // measures nor penalises one hand's surface inside the other's.
 //
 // One launch, one workgroup of 1,024 lanes per row = (sample, hand); lane t owns vertex t of hand h, and the mesh is the OTHER hand's.
-//   LDS (IcpShared, icp_common.h): the other hand's vertices as x / y / z planes (12 KB), its faces as 16-bit triples (16 KB), and ALL its
+//   LDS (IcpShared, mesh_geom.h): the other hand's vertices as x / y / z planes (12 KB), its faces as 16-bit triples (16 KB), and ALL its
 //   triangles as their three corners in face order, 48 B a triangle (96 KB): both loops read the list front to back, every lane the same
 //   triangle, three broadcast 16-byte reads.
-//   Inside: the generalized winding number by mesh_penetration_kernel's forms (metrics.hip) -- the corners relative to the vertex, the
-//   Van Oosterom-Strackee numerator from separately rounded products, atan2f, summed in double in ascending face order, the same scaling and
-//   the same fp32 comparison with 0.5, each triangle's term rounded as that kernel rounds it (pl_solid_angle).  The corner list holds the very
-//   floats metrics.hip reads from its planes, so `inside` is its wind > 0.5.
-//   Closest point: icp_walk<true> (icp_common.h), the device code behind pdf_mesh_icp and pdf_cloud_mesh_loss, over the whole list.  Only a
-//   wave that holds an inside vertex walks (wave-uniform); separated hands walk nothing.
+//   Inside: the generalized winding number of mesh_penetration_kernel (metrics.hip) -- the corners relative to the vertex, each triangle's
+//   term by the function both kernels call (geo_solid_angle), atan2f, summed in double in ascending face order, the same scaling and the same
+//   fp32 comparison with 0.5.  The corner list holds the very floats metrics.hip reads from its planes, so `inside` is its wind > 0.5
+//   (tests/test_penetration_loss_gpu.py compares the two entry points bit for bit).
+//   Closest point: icp_walk<true>, the device code behind pdf_mesh_icp and pdf_cloud_mesh_loss, over the whole list.  Only a wave that holds
+//   an inside vertex walks (wave-uniform); separated hands walk nothing.
 //   loss = (1/n) sum |v - q|^2 over the inside vertices, by the fixed-order block sum.  grad_self of an inside vertex is (2/n)(v - q).
-//   grad_other, without atomics (cloud_mesh_loss_kernel's gather): behind the block sum's barriers the corner list is dead and lane t writes
-//   vertex t's record over its head: s.ca[t] = (wa, wb, wc, corner indices 0 and 1 as 16-bit halves), s.cb[t] = (-(2/n)(v - q), corner index
-//   2); a vertex that is not inside writes the index 0xffff, which is no vertex.  Lane t < n then reads the n records front to back, every lane
-//   the same record, and adds those that name vertex t of the other hand, in double, in ascending vertex order.  A row writes only its own
-//   row of both gradient tensors, so nothing is accumulated across workgroups.
-#include "common.h"
-#include "svd3.h"
-#include "icp_common.h"                                         // IcpShared, icp_walk, icp_block_sum
-
-// Numerator and denominator of a triangle's Van Oosterom-Strackee solid angle, a, b, c the corners relative to the query:
-//   det = a . (b x c),  den = |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|
-// mesh_penetration_kernel (metrics.hip) writes these as plain expressions and leaves their contraction to the compiler; which products it fuses
-// there depends on the code around them, and the same expressions here were fused differently (winding numbers 1e-6 apart, enough to
-// move a vertex across 0.5).  So the roundings that kernel is BUILT with are spelled out here, fused multiply-adds and separately rounded
-// products alike, with contraction off: `inside` is that kernel's wind > 0.5 bit for bit, whatever surrounds this function.
-// tests/test_penetration_loss_gpu.py compares the two entry points on the template hands.
-__device__ __forceinline__ void pl_solid_angle(float ax, float ay, float az, float bx, float by, float bz, float cx, float cy, float cz,
-                                               float& det, float& den) {
-#pragma clang fp contract(off)
-    const float la = sqrtf(__builtin_fmaf(ay, ay, ax * ax) + az * az);
-    const float lb = sqrtf(__builtin_fmaf(by, by, bx * bx) + bz * bz);
-    const float lc = sqrtf(__builtin_fmaf(cx, cx, cy * cy) + cz * cz);
-    const float ab = __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
-    const float bc = bz * cz + __builtin_fmaf(by, cy, bx * cx);
-    const float ca = __builtin_fmaf(ax, cx, ay * cy) + az * cz;
-    const float ux = by * cz - bz * cy, uy = bz * cx - bx * cz, uz = bx * cy - by * cx;      // b x c from separately rounded products
-    det = az * uz + __builtin_fmaf(ay, uy, ax * ux);
-    den = lb * ca + __builtin_fmaf(la, bc, __builtin_fmaf(ab, lc, (la * lb) * lc));
-}
+//   grad_other, without atomics: geo_corner_gather over the n records of the row's vertices, each carrying -(2/n)(v - q); lane t < n gets the
+//   sum for vertex t of the other hand.  A row writes only its own row of both gradient tensors, so nothing is accumulated across workgroups.
+#include "mesh_geom.h"
 
 __global__ __launch_bounds__(ICP_T) void penetration_loss_kernel(const float* __restrict__ verts, const long long* __restrict__ faces,
                                                                  const float* __restrict__ valid, int n, int Fc, float* __restrict__ loss,
@@ -66,19 +40,8 @@ __global__ __launch_bounds__(ICP_T) void penetration_loss_kernel(const float* __
         return;
     }
     const float* other = verts + (row ^ 1) * n * 3;            // rows 2b, 2b + 1 are the two hands of sample b
-    for (int e = t; e < 3 * n; e += ICP_T) {
-        const int i = e / 3, k = e - 3 * i;
-        (k == 0 ? s.vx : k == 1 ? s.vy : s.vz)[i] = other[e];
-    }
-    const long long* fo = faces + (long)(1 - h) * Fc * 3;
-    for (int g = t; g < Fc; g += ICP_T) {
-        ushort4 f;                                             // an index outside [0, n) is clamped: it must not leave the staged planes
-        f.x = (unsigned short)min(max(fo[3 * g + 0], 0LL), (long long)(n - 1));
-        f.y = (unsigned short)min(max(fo[3 * g + 1], 0LL), (long long)(n - 1));
-        f.z = (unsigned short)min(max(fo[3 * g + 2], 0LL), (long long)(n - 1));
-        f.w = 0;
-        s.tri[g] = f;
-    }
+    geo_stage_planes(other, n, s.vx, s.vy, s.vz);
+    geo_stage_faces(faces + (long)(1 - h) * Fc * 3, Fc, n, s.tri);
     __syncthreads();
     for (int g = t; g < Fc; g += ICP_T) {                      // every triangle is listed, in face order; ca.w carries the face index
         const ushort4 f = s.tri[g];
@@ -99,7 +62,7 @@ __global__ __launch_bounds__(ICP_T) void penetration_loss_kernel(const float* __
             const float bx = B.x - x, by = B.y - y, bz = B.z - z;
             const float cx = C.x - x, cy = C.y - y, cz = C.z - z;
             float det, den;
-            pl_solid_angle(ax, ay, az, bx, by, bz, cx, cy, cz, det, den);
+            geo_solid_angle(ax, ay, az, bx, by, bz, cx, cy, cz, det, den);
             omega += (double)atan2f(det, den);
         }
         const float w = (float)(omega * (2.0 / (4.0 * 3.14159265358979323846)));
@@ -129,24 +92,11 @@ __global__ __launch_bounds__(ICP_T) void penetration_loss_kernel(const float* __
         if (t < n) { float* g = grad_other + at * 3; g[0] = g[1] = g[2] = 0.f; }
         return;
     }
+    // (an inside lane's walk found a face: Fc >= 1)
+    const double3 go = geo_corner_gather(s, wa, wb, wc, -gx, -gy, -gz, in ? face : -1, n, n);
     if (t < n) {
-        ushort4 f = make_ushort4(0xffff, 0xffff, 0xffff, 0);
-        if (in) f = s.tri[face];                               // 0 <= face < Fc: Fc >= 1, so an inside lane's walk found one
-        s.ca[t] = make_float4(wa, wb, wc, __int_as_float((int)f.x | ((int)f.y << 16)));
-        s.cb[t] = make_float4(-gx, -gy, -gz, __int_as_float((int)f.z));
-    }
-    __syncthreads();
-    if (t < n) {
-        double sx = 0.0, sy = 0.0, sz = 0.0;
-        for (int j = 0; j < n; ++j) {
-            const float4 ra = s.ca[j], rb = s.cb[j];
-            const int i01 = __float_as_int(ra.w), i2 = __float_as_int(rb.w);
-            if ((i01 & 0xffff) == t) { sx += (double)(ra.x * rb.x); sy += (double)(ra.x * rb.y); sz += (double)(ra.x * rb.z); }
-            if (((i01 >> 16) & 0xffff) == t) { sx += (double)(ra.y * rb.x); sy += (double)(ra.y * rb.y); sz += (double)(ra.y * rb.z); }
-            if (i2 == t) { sx += (double)(ra.z * rb.x); sy += (double)(ra.z * rb.y); sz += (double)(ra.z * rb.z); }
-        }
         float* g = grad_other + at * 3;
-        g[0] = (float)sx; g[1] = (float)sy; g[2] = (float)sz;
+        g[0] = (float)go.x; g[1] = (float)go.y; g[2] = (float)go.z;
     }
 }
 
@@ -154,7 +104,7 @@ PDF_API int pdf_penetration_loss(const float* verts, const long long* faces, con
                                  float* grad_self, float* grad_other, int* inside, int* tri, float* bary, float* closest, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (n < 1 || n > ICP_MAXN || Fc < 1 || Fc > ICP_MAXF || verts == nullptr || faces == nullptr || loss == nullptr || count == nullptr)
+    if (n < 1 || n > HAND_MAXN || Fc < 1 || Fc > HAND_MAXF || verts == nullptr || faces == nullptr || loss == nullptr || count == nullptr)
         return PDF_E_BADARG;
     hipLaunchKernelGGL(penetration_loss_kernel, dim3(2 * B), dim3(ICP_T), 0, s, verts, faces, valid, n, Fc, loss, count, grad_self, grad_other,
                        inside, tri, bary, closest);

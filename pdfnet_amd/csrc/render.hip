@@ -33,22 +33,13 @@
 //   broadcast) with its winner in registers; the epilogue writes face / depth / bary and shades.
 //   render_compare_kernel: one block of 1,024 threads per sample, integer counts and a double sum per thread over a fixed pixel stride, reduced
 //   by wave shuffles and a fixed-order finish in thread 0.
-#include "common.h"
+#include "mesh_geom.h"                                          // HAND_MAXN, HAND_MAXF, geo_det2, geo_index, geo_project
 
 #define RND_T 256
 #define RND_TILE 16
-#define RND_MAXN 1024
-#define RND_MAXF 2048
 #define RND_MAXM 32
 #define RND_MAXHW 2048
 #define RND_CMP_T 1024
-
-// p q - r s from separately rounded products (no fma): exactly negated when (p, r) or (q, s) are
-__device__ __forceinline__ float rnd_det2(float p, float q, float r, float s) {
-#pragma clang fp contract(off)
-    return p * q - r * s;
-}
-__device__ __forceinline__ int rnd_index(const long long* f, int n) { return (int)min(max(*f, 0LL), (long long)(n - 1)); }
 
 __global__ __launch_bounds__(RND_T) void render_vertex_kernel(const float* __restrict__ verts, const long long* __restrict__ faces,
                                                               const float* __restrict__ K, const int* __restrict__ table, long total, int n, int Fc,
@@ -57,10 +48,8 @@ __global__ __launch_bounds__(RND_T) void render_vertex_kernel(const float* __res
     if (e >= total) return;
     const long bh = e / n;
     const int i = (int)(e - bh * n), h = (int)(bh & 1);
-    const float* k = K + (bh >> 1) * 9;
     const float* p = verts + e * 3;
-    const float X = p[0], Y = p[1], Z = p[2];
-    scr[e] = make_float4(k[0] * X / Z + k[2], k[4] * Y / Z + k[5], 1.f / Z, Z);
+    scr[e] = geo_project(K + (bh >> 1) * 9, p[0], p[1], p[2]);
     if (!normals) return;
     const float* hv = verts + bh * n * 3;
     const long long* hf = faces + (long)h * Fc * 3;
@@ -68,9 +57,9 @@ __global__ __launch_bounds__(RND_T) void render_vertex_kernel(const float* __res
     for (int m = 0; m < M; ++m) {
         const int f = table[((long)h * n + i) * M + m];
         if (f < 0 || f >= Fc) continue;
-        const float* a = hv + 3 * rnd_index(hf + 3 * f, n);
-        const float* b = hv + 3 * rnd_index(hf + 3 * f + 1, n);
-        const float* c = hv + 3 * rnd_index(hf + 3 * f + 2, n);
+        const float* a = hv + 3 * geo_index(hf + 3 * f, n);
+        const float* b = hv + 3 * geo_index(hf + 3 * f + 1, n);
+        const float* c = hv + 3 * geo_index(hf + 3 * f + 2, n);
         const float ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2], vx = c[0] - a[0], vy = c[1] - a[1], vz = c[2] - a[2];
         nx += uy * vz - uz * vy;
         ny += uz * vx - ux * vz;
@@ -105,10 +94,10 @@ __global__ __launch_bounds__(RND_T) void render_tile_kernel(const float* __restr
             const int h = g >= Fc;
             if (h ? ok_right : ok_left) {
                 const long long* f = faces + (long)g * 3;          // [2][Fc][3]: row g
-                const int idx[3] = {rnd_index(f, n), rnd_index(f + 1, n), rnd_index(f + 2, n)};
+                const int idx[3] = {geo_index(f, n), geo_index(f + 1, n), geo_index(f + 2, n)};
                 const float4* sv = scr + (b * 2 + h) * n;
                 const float4 v[3] = {sv[idx[0]], sv[idx[1]], sv[idx[2]]};
-                const float a2 = rnd_det2(v[1].x - v[0].x, v[2].y - v[0].y, v[2].x - v[0].x, v[1].y - v[0].y);
+                const float a2 = geo_det2(v[1].x - v[0].x, v[2].y - v[0].y, v[2].x - v[0].x, v[1].y - v[0].y);
                 const bool front = v[0].w >= z_near && v[1].w >= z_near && v[2].w >= z_near;
                 const float lox = fminf(fminf(v[0].x, v[1].x), v[2].x), hix = fmaxf(fmaxf(v[0].x, v[1].x), v[2].x);
                 const float loy = fminf(fminf(v[0].y, v[1].y), v[2].y), hiy = fmaxf(fmaxf(v[0].y, v[1].y), v[2].y);
@@ -143,9 +132,9 @@ __global__ __launch_bounds__(RND_T) void render_tile_kernel(const float* __restr
         __syncthreads();
         for (int j = 0; j < count; ++j) {
             const float4 f0 = list[j * 4 + 0], f1 = list[j * 4 + 1], f2 = list[j * 4 + 2], fz = list[j * 4 + 3];
-            const float w0 = rnd_det2(f0.z, py - f0.y, f0.w, px - f0.x);
-            const float w1 = rnd_det2(f1.z, py - f1.y, f1.w, px - f1.x);
-            const float w2 = rnd_det2(f2.z, py - f2.y, f2.w, px - f2.x);
+            const float w0 = geo_det2(f0.z, py - f0.y, f0.w, px - f0.x);
+            const float w1 = geo_det2(f1.z, py - f1.y, f1.w, px - f1.x);
+            const float w2 = geo_det2(f2.z, py - f2.y, f2.w, px - f2.x);
             const float ws = w0 + w1 + w2;
             if (w0 >= 0.f && w1 >= 0.f && w2 >= 0.f && ws > 0.f) {
                 const float q0 = w0 * fz.x, q1 = w1 * fz.y, q2 = w2 * fz.z, q = q0 + q1 + q2;
@@ -167,7 +156,7 @@ __global__ __launch_bounds__(RND_T) void render_tile_kernel(const float* __restr
     if (hit) {
         const int h = bid >= Fc;
         const long long* f = faces + (long)bid * 3;
-        const int i0 = rnd_index(f, n), i1 = rnd_index(f + 1, n), i2 = rnd_index(f + 2, n);
+        const int i0 = geo_index(f, n), i1 = geo_index(f + 1, n), i2 = geo_index(f + 2, n);
         const long vb = (b * 2 + h) * n;
         const float* cl = colour + b * colour_stride + (long)h * n * 3;
         r = b0 * cl[3 * i0] + b1 * cl[3 * i1] + b2 * cl[3 * i2];
@@ -203,7 +192,7 @@ PDF_API int pdf_render_hands(const float* verts, const long long* faces, const f
                              int* face, float* depth, float* bary, float* rgb, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (n < 1 || n > RND_MAXN || Fc < 1 || Fc > RND_MAXF || H < 1 || H > RND_MAXHW || W < 1 || W > RND_MAXHW || M < 1 || M > RND_MAXM || B > 65535)
+    if (n < 1 || n > HAND_MAXN || Fc < 1 || Fc > HAND_MAXF || H < 1 || H > RND_MAXHW || W < 1 || W > RND_MAXHW || M < 1 || M > RND_MAXM || B > 65535)
         return PDF_E_BADARG;
     if (verts == nullptr || faces == nullptr || K == nullptr || scratch == nullptr || face == nullptr || depth == nullptr || !(z_near > 0.f))
         return PDF_E_BADARG;
@@ -266,7 +255,7 @@ PDF_API int pdf_render_compare(const int* face_pred, const int* face_gt, const f
                                int* iou, float* res, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (Fc < 1 || Fc > RND_MAXF || H < 1 || H > RND_MAXHW || W < 1 || W > RND_MAXHW) return PDF_E_BADARG;
+    if (Fc < 1 || Fc > HAND_MAXF || H < 1 || H > RND_MAXHW || W < 1 || W > RND_MAXHW) return PDF_E_BADARG;
     if (face_pred == nullptr || face_gt == nullptr || iou == nullptr || (sensor != nullptr && (depth_pred == nullptr || res == nullptr))) return PDF_E_BADARG;
     hipLaunchKernelGGL(render_compare_kernel, dim3(B), dim3(RND_CMP_T), 0, s, face_pred, face_gt, depth_pred, sensor, H * W, Fc, iou, res);
     PDF_LAUNCH_CHECK();

@@ -1,8 +1,8 @@
 // Differentiable soft-silhouette loss of the two hand meshes against per-hand masks (contract: pdf_silhouette_loss in pdfnet_hip.h).  The
 // reference's legacy branch trained on pytorch3d's rendered masks (lib/trains/simplified.py); csrc/render.hip is the hard rasteriser behind
 // the evaluation's silhouette IoU and has no gradient.  Here every triangle is a sigmoid of its signed squared screen distance and the
-// triangles of a hand are aggregated as a product: no z-buffer, no coverage decision, smooth by construction.  Projection and pixel centres
-// are render.hip's.  Deterministic, no atomics: two runs are bit-identical.
+// triangles of a hand are aggregated as a product: no z-buffer, no coverage decision, smooth by construction.  The projection (geo_project,
+// mesh_geom.h) and the pixel centres are render.hip's.  Deterministic, no atomics: two runs are bit-identical.
 //
 // DESIGN (five launches; the last two only when a gradient is asked for)
 //   sil_vertex_kernel: one thread per (sample, hand, vertex) writes (x, y, 1/Z, Z) into the scratch.
@@ -21,17 +21,13 @@
 //   floats per lane, reduced by a butterfly; lane 0 writes gface [B,2,Fc,3,2].  A skipped face writes zeros.
 //   sil_vertex_grad_kernel: one thread per vertex gathers gface over the vertex -> face table in ascending face order, finds its corner(s) by
 //   comparing clamped indices, applies the pinhole Jacobian and writes grad.  A vertex without a contribution gets exactly 0.
-#include "common.h"
+#include "mesh_geom.h"                                          // HAND_MAXN, HAND_MAXF, geo_det2, geo_index, geo_project
 
 #define SIL_T 256
 #define SIL_TILE 16
-#define SIL_MAXN 1024
-#define SIL_MAXF 2048
 #define SIL_MAXM 32
 #define SIL_MAXHW 2048
 #define SIL_CUT 16.0f                                           // rho^2 = SIL_CUT sigma: sigmoid(-16) = 1.1e-7 at the inclusion border
-
-__device__ __forceinline__ int sil_index(const long long* f, int n) { return (int)min(max(*f, 0LL), (long long)(n - 1)); }
 
 struct SilFace {
     float x0, y0, x1, y1, x2, y2, s;                            // screen corners, sign(A2)
@@ -43,7 +39,7 @@ __device__ __forceinline__ bool sil_face(const float4 a, const float4 b, const f
 #pragma clang fp contract(off)
     const bool front = a.w >= z_near && b.w >= z_near && c.w >= z_near;                     // (false for a NaN depth)
     const bool finite = isfinite(a.x) && isfinite(a.y) && isfinite(b.x) && isfinite(b.y) && isfinite(c.x) && isfinite(c.y);
-    const float a2 = (b.x - a.x) * (c.y - a.y) - (c.x - a.x) * (b.y - a.y);                 // products rounded separately: a repeated corner gives exactly 0
+    const float a2 = geo_det2(b.x - a.x, c.y - a.y, c.x - a.x, b.y - a.y);                  // products rounded separately: a repeated corner gives exactly 0
     f.x0 = a.x; f.y0 = a.y; f.x1 = b.x; f.y1 = b.y; f.x2 = c.x; f.y2 = c.y;
     f.s = a2 > 0.f ? 1.f : -1.f;
     f.bx0 = fminf(fminf(a.x, b.x), c.x) - rho; f.bx1 = fmaxf(fmaxf(a.x, b.x), c.x) + rho;
@@ -97,10 +93,8 @@ __global__ __launch_bounds__(SIL_T) void sil_vertex_kernel(const float* __restri
                                                            float4* __restrict__ scr) {
     const long e = (long)blockIdx.x * SIL_T + threadIdx.x;       // (b, h, i)
     if (e >= total) return;
-    const float* k = K + (e / n >> 1) * 9;
     const float* p = verts + e * 3;
-    const float X = p[0], Y = p[1], Z = p[2];
-    scr[e] = make_float4(k[0] * X / Z + k[2], k[4] * Y / Z + k[5], 1.f / Z, Z);
+    scr[e] = geo_project(K + (e / n >> 1) * 9, p[0], p[1], p[2]);
 }
 
 __global__ __launch_bounds__(SIL_T) void sil_tile_kernel(const long long* __restrict__ faces, const float* __restrict__ valid,
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(SIL_T) void sil_tile_kernel(const long long* __rest
         SilFace f;
         if (g < Fc) {
             const long long* fi = hf + (long)g * 3;
-            keep = sil_face(sv[sil_index(fi, n)], sv[sil_index(fi + 1, n)], sv[sil_index(fi + 2, n)], z_near, rho, f);
+            keep = sil_face(sv[geo_index(fi, n)], sv[geo_index(fi + 1, n)], sv[geo_index(fi + 2, n)], z_near, rho, f);
             keep = keep && !(f.bx1 < cx0 || f.bx0 > cx1 || f.by1 < cy0 || f.by0 > cy1);
         }
         const unsigned long long m = __ballot(keep);
@@ -220,7 +214,7 @@ __global__ __launch_bounds__(SIL_T) void sil_face_grad_kernel(const long long* _
     if (keep) {
         const long long* fi = faces + ((long)h * Fc + g) * 3;
         const float4* sv = scr + bh * n;
-        keep = sil_face(sv[sil_index(fi, n)], sv[sil_index(fi + 1, n)], sv[sil_index(fi + 2, n)], z_near, rho, f);
+        keep = sil_face(sv[geo_index(fi, n)], sv[geo_index(fi + 1, n)], sv[geo_index(fi + 2, n)], z_near, rho, f);
     }
     // a face whose grown box misses every pixel centre contributes nothing either (its clamped window would hold pixels it does not include)
     keep = keep && f.bx1 >= 0.5f && f.by1 >= 0.5f && f.bx0 <= (float)W - 0.5f && f.by0 <= (float)H - 0.5f;
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(SIL_T) void sil_vertex_grad_kernel(const float* __r
         if (f < 0 || f >= Fc) continue;
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            if (sil_index(hf + 3 * f + k, n) == i) { gx += gf[f * 6 + 2 * k]; gy += gf[f * 6 + 2 * k + 1]; }
+            if (geo_index(hf + 3 * f + k, n) == i) { gx += gf[f * 6 + 2 * k]; gy += gf[f * 6 + 2 * k + 1]; }
     }
     float* o = grad + e * 3;
     if (gx == 0.f && gy == 0.f) {                                  // in no face, or only in skipped ones (whatever its Z): exactly 0
@@ -294,7 +288,7 @@ PDF_API int pdf_silhouette_loss(const float* verts, const long long* faces, cons
                                 float* scratch, float* loss, float* sums, float* trans, float* grad, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0) return 0;
-    if (n < 1 || n > SIL_MAXN || Fc < 1 || Fc > SIL_MAXF || H < 1 || H > SIL_MAXHW || W < 1 || W > SIL_MAXHW || M < 1 || M > SIL_MAXM || B > 65535)
+    if (n < 1 || n > HAND_MAXN || Fc < 1 || Fc > HAND_MAXF || H < 1 || H > SIL_MAXHW || W < 1 || W > SIL_MAXHW || M < 1 || M > SIL_MAXM || B > 65535)
         return PDF_E_BADARG;
     if (verts == nullptr || faces == nullptr || K == nullptr || mask == nullptr || scratch == nullptr || loss == nullptr || sums == nullptr ||
         trans == nullptr || !(sigma > 0.f) || !(z_near > 0.f) || !(sigma <= 3.0e38f))

@@ -2,12 +2,6 @@
 #pragma once
 #include "common.h"
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // M = U S V^T by one-sided Jacobi (Hestenes) rotations of the columns of G = M V, which converge to U S with V the accumulated rotations.
 // u[c] / v[c]: COLUMN c of U / V, sg descending.  A singular direction whose sigma is below 1e-12 of the largest gets its left vector from the
 // orthogonal complement of the others instead of from rounding noise, so U stays orthogonal for any rank.  Returns false, with sg alone

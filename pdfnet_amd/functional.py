@@ -2433,19 +2433,40 @@ def mesh_nn_counts(pred, gt, thresholds, return_dist=False):
     return (counts, d_gt, d_pred) if return_dist else counts
 
 
+# The limits of the kernels that stage a hand mesh in LDS (csrc/mesh_geom.h: HAND_MAXN, HAND_MAXF, HAND_MAXP), and of a grid's z dimension.
+HAND_MAX_VERTS, HAND_MAX_FACES, HAND_MAX_POINTS = 1024, 2048, 1024
+RENDER_MAX_SAMPLES = 65535
+
+
+def _hand_args(name, verts, faces, valid=None):
+    """The checks every function on the two hand meshes shares -> (verts [..., 2, n, 3] f32, faces [2, Fc, 3] int64, valid [..., 2] f32 or
+    None, detached and contiguous, lead = the shape [..., 2], n, Fc).  Raises ValueError; the caller asks for the GPU."""
+    v, f = verts.detach().float().contiguous(), faces.detach().long().contiguous()
+    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
+        raise ValueError("pdfnet_amd: %s wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (name, tuple(v.shape), tuple(f.shape)))
+    lead, n, Fc = v.shape[:-2], v.shape[-2], f.shape[1]
+    if not (1 <= n <= HAND_MAX_VERTS and 1 <= Fc <= HAND_MAX_FACES):
+        raise ValueError("pdfnet_amd: %s takes 1 to %d vertices and 1 to %d faces per hand, got %d and %d" % (name, HAND_MAX_VERTS, HAND_MAX_FACES, n, Fc))
+    va = None
+    if valid is not None:
+        va = valid.detach().float().contiguous()
+        if va.shape != lead:
+            raise ValueError("pdfnet_amd: %s wants valid %s, got %s" % (name, tuple(lead), tuple(va.shape)))
+    return v, f, va, lead, n, Fc
+
+
+def _scaled_grad(ctx, g, inputs):
+    """backward of a loss [..., 2] whose forward launch left d loss / d verts in ctx.grad, verts being the first of `inputs` arguments."""
+    return ((g[..., None, None] * ctx.grad).to(ctx.dtype),) + (None,) * (inputs - 1)
+
+
 def mesh_penetration(verts, faces, return_fields=False):
     """verts [..., 2, n, 3] (left, right hand), faces [2, Fc, 3] int64 (left, right: the loss module's `faces_pair`) -> per hand, its vertices
     against the OTHER hand's mesh: (count int32 [..., 2] of vertices whose generalized winding number exceeds 0.5, depth [..., 2] = the largest
     distance to the other surface among them (0 without any), gap [..., 2] = the smallest distance of any vertex to the other surface).
     return_fields: also (wind, dist) [..., 2, n].  n <= 1024, Fc <= 2048 (csrc/metrics.hip stages a mesh in LDS).  No gradient."""
     hip.require_gpu(verts, faces)
-    v, f = verts.detach().float().contiguous(), faces.detach().long().contiguous()
-    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
-        raise ValueError("pdfnet_amd: mesh_penetration wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
-    n, Fc = v.shape[-2], f.shape[1]
-    if not (1 <= n <= 1024 and 1 <= Fc <= 2048):
-        raise ValueError("pdfnet_amd: mesh_penetration takes 1 to 1024 vertices and 1 to 2048 faces per hand, got %d and %d" % (n, Fc))
-    lead = v.shape[:-2]
+    v, f, _, lead, n, Fc = _hand_args('mesh_penetration', verts, faces)
     count = torch.empty(lead, dtype=torch.int32, device=v.device)
     depth, gap = (torch.empty(lead, dtype=torch.float32, device=v.device) for _ in range(2))
     wind, dist = (torch.empty(v.shape[:-1], dtype=torch.float32, device=v.device) for _ in range(2)) if return_fields else (None, None)
@@ -2458,22 +2479,16 @@ def _cloud_args(name, verts, faces, cloud, valid, trim):
     f32 / int64 tensors,
     lead, n, Fc, P, trim)."""
     hip.require_gpu(verts, faces, cloud, valid)
-    v, f, c = verts.detach().float().contiguous(), faces.detach().long().contiguous(), cloud.detach().float().contiguous()
-    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
-        raise ValueError("pdfnet_amd: %s wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (name, tuple(v.shape), tuple(f.shape)))
-    lead, n, Fc = v.shape[:-2], v.shape[-2], f.shape[1]
+    v, f, va, lead, n, Fc = _hand_args(name, verts, faces, valid)
+    c = cloud.detach().float().contiguous()
     if c.dim() != v.dim() or c.shape[:-2] != lead or c.shape[-1] != 3:
         raise ValueError("pdfnet_amd: %s wants cloud %s for verts %s, got %s" % (name, tuple(lead) + ('P', 3), tuple(v.shape), tuple(c.shape)))
     P, trim = c.shape[-2], float(trim)
-    if not (1 <= n <= 1024 and 1 <= Fc <= 2048 and 1 <= P <= 1024):
-        raise ValueError("pdfnet_amd: %s takes 1 to 1024 vertices, 1 to 2048 faces and 1 to 1024 points per hand, got %d, %d and %d" % (name, n, Fc, P))
+    if not 1 <= P <= HAND_MAX_POINTS:
+        raise ValueError("pdfnet_amd: %s takes 1 to %d vertices, 1 to %d faces and 1 to %d points per hand, got %d, %d and %d" % (
+            name, HAND_MAX_VERTS, HAND_MAX_FACES, HAND_MAX_POINTS, n, Fc, P))
     if not 0.0 < trim < float('inf'):
         raise ValueError("pdfnet_amd: %s takes a finite trim > 0, got %r" % (name, trim))
-    va = None
-    if valid is not None:
-        va = valid.detach().float().contiguous()
-        if va.shape != lead:
-            raise ValueError("pdfnet_amd: %s wants valid %s, got %s" % (name, tuple(lead), tuple(va.shape)))
     return v, f, c, va, lead, n, Fc, P, trim
 
 
@@ -2522,7 +2537,7 @@ class _CloudMeshLoss(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g, *unused):
-        return (g[..., None, None] * ctx.grad).to(ctx.dtype), None, None, None, None, None, None
+        return _scaled_grad(ctx, g, 7)
 
 
 def cloud_mesh_loss(verts, faces, cloud, valid=None, trim=0.03, return_fields=False):
@@ -2561,7 +2576,7 @@ class _MeshCloudLoss(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g, *unused):
-        return (g[..., None, None] * ctx.grad).to(ctx.dtype), None, None, None, None, None, None, None
+        return _scaled_grad(ctx, g, 8)
 
 
 def mesh_cloud_loss(verts, faces, cloud, valid=None, trim=0.03, margin=0.002, return_fields=False):
@@ -2586,17 +2601,7 @@ class _PenetrationLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, faces, valid, fields, want_grad):
         hip.require_gpu(verts, faces, valid)
-        v, f = verts.detach().float().contiguous(), faces.detach().long().contiguous()
-        if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
-            raise ValueError("pdfnet_amd: penetration_loss wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
-        lead, n, Fc = v.shape[:-2], v.shape[-2], f.shape[1]
-        if not (1 <= n <= 1024 and 1 <= Fc <= 2048):
-            raise ValueError("pdfnet_amd: penetration_loss takes 1 to 1024 vertices and 1 to 2048 faces per hand, got %d and %d" % (n, Fc))
-        va = None
-        if valid is not None:
-            va = valid.detach().float().contiguous()
-            if va.shape != lead:
-                raise ValueError("pdfnet_amd: penetration_loss wants valid %s, got %s" % (tuple(lead), tuple(va.shape)))
+        v, f, va, lead, n, Fc = _hand_args('penetration_loss', verts, faces, valid)
         dev = v.device
         loss, count = torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev)
         grad_self, grad_other = (torch.empty_like(v), torch.empty_like(v)) if want_grad else (None, None)
@@ -2660,6 +2665,16 @@ def vertex_face_table(faces, n=None):
     return table.to(faces.device)
 
 
+def _table_arg(name, table, f, n):
+    """A caller's vertex -> face table, or the one built from faces f when it hands in none -> (table int32 [2, n, M] contiguous, M)."""
+    if table is None:
+        table = vertex_face_table(f, n)
+    table = table.detach().int().contiguous()
+    if table.dim() != 3 or table.shape[:2] != (2, n) or not 1 <= table.shape[2] <= RENDER_MAX_DEGREE:
+        raise ValueError("pdfnet_amd: %s wants table [2, %d, 1..%d] (vertex_face_table), got %s" % (name, n, RENDER_MAX_DEGREE, tuple(table.shape)))
+    return table, table.shape[2]
+
+
 def render_hands(verts, faces, K, size, valid=None, colour=None, table=None, ambient_only=False, z_near=0.01, return_bary=False):
     """verts [..., 2, n, 3] camera-space metres (left, right hand), faces [2, Fc, 3] int64 (the loss module's `faces_pair`), K [..., 3, 3],
     size = (H, W) -> (face int32 [..., H, W]: the visible face, 0 .. Fc-1 left, Fc .. 2Fc-1 right, -1 background; depth [..., H, W]: its Z,
@@ -2670,46 +2685,32 @@ def render_hands(verts, faces, K, size, valid=None, colour=None, table=None, amb
     vertex nearer than z_near is skipped.  The arithmetic contract is the header comment of csrc/render.hip.  n <= 1024, Fc <= 2048,
     H, W <= 2048.  No gradient; deterministic."""
     hip.require_gpu(verts, faces, K, valid, colour, table)
-    v, f, k = verts.detach().float().contiguous(), faces.detach().long().contiguous(), K.detach().float().contiguous()
-    if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
-        raise ValueError("pdfnet_amd: render_hands wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
-    lead, n, Fc = v.shape[:-3], v.shape[-2], f.shape[1]
+    v, f, va, hands, n, Fc = _hand_args('render_hands', verts, faces, valid)
+    k, lead = K.detach().float().contiguous(), hands[:-1]
     if k.shape != lead + (3, 3):
         raise ValueError("pdfnet_amd: render_hands wants K %s for verts %s, got %s" % (tuple(lead) + (3, 3), tuple(v.shape), tuple(k.shape)))
     try:
         H, W = (int(s) for s in size)
     except (TypeError, ValueError):
         raise ValueError("pdfnet_amd: render_hands wants size = (H, W), got %r" % (size,))
-    if not (1 <= n <= 1024 and 1 <= Fc <= 2048 and 1 <= H <= 2048 and 1 <= W <= 2048):
-        raise ValueError("pdfnet_amd: render_hands takes 1 to 1024 vertices and 1 to 2048 faces per hand and images of 1 to 2048 pixels a side, "
-                         "got n = %d, Fc = %d, size = (%d, %d)" % (n, Fc, H, W))
+    if not (1 <= H <= 2048 and 1 <= W <= 2048):
+        raise ValueError("pdfnet_amd: render_hands takes 1 to %d vertices and 1 to %d faces per hand and images of 1 to 2048 pixels a side, "
+                         "got n = %d, Fc = %d, size = (%d, %d)" % (HAND_MAX_VERTS, HAND_MAX_FACES, n, Fc, H, W))
     if not z_near > 0:
         raise ValueError("pdfnet_amd: render_hands wants z_near > 0, got %r" % (z_near,))
     B = v.numel() // (2 * n * 3)
-    if B > 65535:
-        raise ValueError("pdfnet_amd: render_hands takes at most 65535 samples a call, got %d" % B)
-    va = None
-    if valid is not None:
-        va = valid.detach().float().contiguous()
-        if va.shape != lead + (2,):
-            raise ValueError("pdfnet_amd: render_hands wants valid %s, got %s" % (tuple(lead) + (2,), tuple(va.shape)))
+    if B > RENDER_MAX_SAMPLES:
+        raise ValueError("pdfnet_amd: render_hands takes at most %d samples a call, got %d" % (RENDER_MAX_SAMPLES, B))
     col, per_sample, M = None, 0, 1
+    if colour is None or ambient_only:
+        table = None                                               # no vertex normals: the kernel gets no table
     if colour is not None:
         col = colour.detach().float().contiguous()
         if col.shape not in ((2, n, 3), tuple(v.shape)):
             raise ValueError("pdfnet_amd: render_hands wants colour [2, %d, 3] or %s, got %s" % (n, tuple(v.shape), tuple(col.shape)))
         per_sample = int(col.dim() > 3)
         if not ambient_only:
-            if table is None:
-                table = vertex_face_table(f, n)
-            table = table.detach().int().contiguous()
-            if table.dim() != 3 or table.shape[:2] != (2, n) or not 1 <= table.shape[2] <= RENDER_MAX_DEGREE:
-                raise ValueError("pdfnet_amd: render_hands wants table [2, %d, 1..%d] (vertex_face_table), got %s" % (n, RENDER_MAX_DEGREE, tuple(table.shape)))
-            M = table.shape[2]
-        else:
-            table = None
-    else:
-        table = None
+            table, M = _table_arg('render_hands', table, f, n)
     dev = v.device
     face = torch.empty(lead + (H, W), dtype=torch.int32, device=dev)
     depth = torch.empty(lead + (H, W), dtype=torch.float32, device=dev)
@@ -2726,45 +2727,30 @@ class _SilhouetteLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, faces, K, mask, weight, valid, sigma, table, z_near, fields, want_grad):
-        v, f, k = verts.detach().float().contiguous(), faces.detach().long().contiguous(), K.detach().float().contiguous()
-        if v.dim() < 3 or v.shape[-1] != 3 or v.shape[-3] != 2 or f.dim() != 3 or f.shape[0] != 2 or f.shape[2] != 3:
-            raise ValueError("pdfnet_amd: silhouette_loss wants verts [..., 2, n, 3] and faces [2, Fc, 3], got %s and %s" % (tuple(v.shape), tuple(f.shape)))
-        lead, n, Fc = v.shape[:-3], v.shape[-2], f.shape[1]
+        v, f, va, hands, n, Fc = _hand_args('silhouette_loss', verts, faces, valid)
+        k, lead = K.detach().float().contiguous(), hands[:-1]
         if k.shape != lead + (3, 3):
             raise ValueError("pdfnet_amd: silhouette_loss wants K %s for verts %s, got %s" % (tuple(lead) + (3, 3), tuple(v.shape), tuple(k.shape)))
         m = mask.detach().float().contiguous()
         if m.dim() != len(lead) + 3 or m.shape[:-2] != lead + (2,):
             raise ValueError("pdfnet_amd: silhouette_loss wants mask %s + (H, W) for verts %s, got %s" % (tuple(lead) + (2,), tuple(v.shape), tuple(m.shape)))
         H, W = m.shape[-2:]
-        if not (1 <= n <= 1024 and 1 <= Fc <= 2048 and 1 <= H <= 2048 and 1 <= W <= 2048):
-            raise ValueError("pdfnet_amd: silhouette_loss takes 1 to 1024 vertices and 1 to 2048 faces per hand and masks of 1 to 2048 pixels a side, "
-                             "got n = %d, Fc = %d, size = (%d, %d)" % (n, Fc, H, W))
+        if not (1 <= H <= 2048 and 1 <= W <= 2048):
+            raise ValueError("pdfnet_amd: silhouette_loss takes 1 to %d vertices and 1 to %d faces per hand and masks of 1 to 2048 pixels a side, "
+                             "got n = %d, Fc = %d, size = (%d, %d)" % (HAND_MAX_VERTS, HAND_MAX_FACES, n, Fc, H, W))
         if not sigma > 0 or not sigma < float('inf'):
             raise ValueError("pdfnet_amd: silhouette_loss wants a finite sigma > 0 (px^2), got %r" % (sigma,))
         if not z_near > 0:
             raise ValueError("pdfnet_amd: silhouette_loss wants z_near > 0, got %r" % (z_near,))
         B = v.numel() // (2 * n * 3)
-        if B > 65535:
-            raise ValueError("pdfnet_amd: silhouette_loss takes at most 65535 samples a call, got %d" % B)
-        wt = va = None
+        if B > RENDER_MAX_SAMPLES:
+            raise ValueError("pdfnet_amd: silhouette_loss takes at most %d samples a call, got %d" % (RENDER_MAX_SAMPLES, B))
+        wt = None
         if weight is not None:
             wt = weight.detach().float().contiguous()
             if wt.shape != m.shape:
                 raise ValueError("pdfnet_amd: silhouette_loss wants weight %s, got %s" % (tuple(m.shape), tuple(wt.shape)))
-        if valid is not None:
-            va = valid.detach().float().contiguous()
-            if va.shape != lead + (2,):
-                raise ValueError("pdfnet_amd: silhouette_loss wants valid %s, got %s" % (tuple(lead) + (2,), tuple(va.shape)))
-        M = 1
-        if want_grad:
-            if table is None:
-                table = vertex_face_table(f, n)
-            table = table.detach().int().contiguous()
-            if table.dim() != 3 or table.shape[:2] != (2, n) or not 1 <= table.shape[2] <= RENDER_MAX_DEGREE:
-                raise ValueError("pdfnet_amd: silhouette_loss wants table [2, %d, 1..%d] (vertex_face_table), got %s" % (n, RENDER_MAX_DEGREE, tuple(table.shape)))
-            M = table.shape[2]
-        else:
-            table = None
+        table, M = _table_arg('silhouette_loss', table, f, n) if want_grad else (None, 1)
         hip.require_gpu(verts, faces, K, mask, weight, valid, table)
         dev = v.device
         loss = torch.empty(lead + (2,), dtype=torch.float32, device=dev)
@@ -2783,7 +2769,7 @@ class _SilhouetteLoss(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g, *unused):
-        return (g[..., None, None] * ctx.grad).to(ctx.dtype), None, None, None, None, None, None, None, None, None, None
+        return _scaled_grad(ctx, g, 11)
 
 
 def silhouette_loss(verts, faces, K, mask, weight=None, valid=None, sigma=1.0, table=None, z_near=0.01, return_fields=False):
@@ -2815,8 +2801,9 @@ def render_compare(face_pred, face_gt, depth_pred, Fc, sensor=None):
         raise ValueError("pdfnet_amd: render_compare wants maps of one shape [..., H, W], got %s, %s, %s%s" % (
             tuple(fp.shape), tuple(fg.shape), tuple(dp.shape), "" if sensor is None else ", %s" % (tuple(sensor.shape),)))
     H, W = fp.shape[-2:]
-    if not (1 <= int(Fc) <= 2048 and 1 <= H <= 2048 and 1 <= W <= 2048):
-        raise ValueError("pdfnet_amd: render_compare takes 1 to 2048 faces per hand and images of 1 to 2048 pixels a side, got Fc = %d, size = (%d, %d)" % (Fc, H, W))
+    if not (1 <= int(Fc) <= HAND_MAX_FACES and 1 <= H <= 2048 and 1 <= W <= 2048):
+        raise ValueError("pdfnet_amd: render_compare takes 1 to %d faces per hand and images of 1 to 2048 pixels a side, got Fc = %d, size = (%d, %d)" % (
+            HAND_MAX_FACES, Fc, H, W))
     sd = sensor.detach().float().contiguous() if sensor is not None else None
     lead = fp.shape[:-2]
     iou = torch.empty(lead + (2, 2), dtype=torch.int32, device=fp.device)

@@ -302,6 +302,48 @@ def test_template_hands_against_the_restatement():
     assert (np.abs(ref['grad_other']).max((2, 3))[1:] > 10 * bar['grad_other'][1:]).all() and (ref['loss'][1:] > 100 * bar['loss'][1:]).all()
 
 
+# ---- the loss's inside set is the metric's, bit for bit ------------------------------------------------------
+def threshold_case():
+    """n = 64, Fc = 4.  Hand 1 is the test tetrahedron, its spare vertices parked on corner 0.  Hand 0's vertices sit on its surface, where
+    the side of 0.5 a vertex falls on is decided by rounding alone (a point on a face sees that face under +-2 pi by the sign of a
+    determinant that is 0 in exact arithmetic, so its winding number is 0 or 1; on an edge or a corner both arguments of atan2 vanish): the
+    4 corners, 2 points on each of the 6 edges and 2 on each of the 4 faces (24), and the first 20 of those moved by +1e-7 m and by -1e-7 m
+    along the direction from the centroid (40).  Hand 0's own faces index its first four vertices."""
+    on = [TET[i] for i in range(4)]
+    on += [(1 - t) * TET[i] + t * TET[j] for i in range(4) for j in range(i + 1, 4) for t in (0.5, 0.3)]
+    on += [w[0] * TET[f[0]] + w[1] * TET[f[1]] + w[2] * TET[f[2]] for f in TET_FACES for w in ((1 / 3, 1 / 3, 1 / 3), (0.6, 0.3, 0.1))]
+    on = np.array(on)
+    out = on[:20] / np.linalg.norm(on[:20], axis=-1, keepdims=True)
+    own = np.concatenate((on, on[:20] + 1e-7 * out, on[:20] - 1e-7 * out))
+    other = TET[np.concatenate((np.arange(4), np.zeros(60, np.int64)))]
+    assert own.shape == other.shape == (64, 3)
+    return np.stack((own, other))[None].astype(np.float32), np.stack((TET_FACES, TET_FACES))
+
+
+def random_case(n=33, Fc=50, seed=7):
+    g = np.random.default_rng(seed)
+    return g.normal(0.0, 0.05, (2, 2, n, 3)).astype(np.float32), g.integers(0, n, (2, Fc, 3)).astype(np.int64)
+
+
+@pytest.mark.parametrize("case", [threshold_case, random_case])
+def test_inside_is_the_metrics_wind_above_half_with_no_condition_on_the_input(case):
+    """Both kernels call one function for a triangle's solid angle (csrc/mesh_geom.h geo_solid_angle) and sum, scale and compare alike, so
+    `inside` IS mesh_penetration's wind > 0.5 and count its count, for every vertex of every input: asserted where rounding alone decides the
+    side (on the other hand's faces, edges and corners, and 1e-7 m off them) and on a seeded random pair of triangle soups.  Nothing is
+    excluded and nothing is compared with float64: the statement is the equality of two kernels' bits."""
+    from pdfnet_amd import functional as F
+    verts, faces = case()
+    with torch.no_grad():
+        _, count, inside, _, _, _ = F.penetration_loss(cu(verts), cu(faces), return_fields=True)
+        m_count, _, _, wind, _ = F.mesh_penetration(cu(verts), cu(faces), return_fields=True)
+    wind, inside = wind.cpu().numpy(), inside.cpu().numpy()
+    print("  %s: inside %s of %d, smallest |wind - 0.5| %.3e, vertices with |wind - 0.5| < 1e-6: %d" % (
+        case.__name__, count.cpu().numpy().tolist(), verts.shape[2], np.abs(wind - 0.5).min(), (np.abs(wind - 0.5) < 1e-6).sum()))
+    assert np.array_equal(inside != 0, wind > 0.5), np.argwhere((inside != 0) != (wind > 0.5))
+    assert np.array_equal(count.cpu().numpy(), m_count.cpu().numpy())
+    assert np.array_equal(count.cpu().numpy(), (wind > 0.5).sum(-1))
+
+
 # ---- sizes -------------------------------------------------------------------------------------------------
 SIZE_SEEDS = {63: 1, 65: 1}                                        # seeds for which the case is well conditioned (tests/test_penetration_loss_cpu.py)
 
