@@ -21,14 +21,13 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_internal.h"), os.path.join(CSRC, "svd3.h"), os.path.join(CSRC, "mesh_geom.h"), os.path.join(INCLUDE, "pdfnet_hip.h")]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_internal.h"), os.path.join(CSRC, "svd3.h"), os.path.join(CSRC, "mesh_geom.h"), os.path.join(CSRC, "meshdec_kernels.h"), os.path.join(INCLUDE, "pdfnet_hip.h")]
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(CSRC, s.replace(".hip", ".o"))
         objs.append(obj)
-        deps = [src] + hdrs + ([os.path.join(CSRC, "meshdec.hip")] if s in ("meshdec_bf16.hip", "meshdec_x3.hip") else [])     # (it #includes meshdec.hip)
-        if force or _stale(obj, deps):
+        if force or _stale(obj, [src] + hdrs):
             jobs.append([hipcc] + FLAGS + ["-c", src, "-o", obj])
 
     def run(cmd):

@@ -330,6 +330,32 @@ def test_rejected_call_leaves_no_armed_slot():
     assert L.pdf_debug_armed_slots() == 0
 
 
+def test_mesh_level_entry_points_reject_a_bad_block_before_any_launch():
+    """The fp32, bf16 and x3 builds of the fused mesh decoder share one argument check (csrc/meshdec_kernels.h: mesh_check, then the backward's
+    own), made before any HIP call: every entry point answers PDF_E_BADARG to a block that fails it.  Each case spoils ONE field of a block that
+    would pass (fake non-null pointers: a block that passes is never sent).  Runs without a GPU."""
+    from pdfnet_amd import hip
+    c = hip.lib().cdll
+
+    def block(**spoil):
+        a = hip.MeshLevel()
+        a.level, a.B, a.training, a.cin0, a.p, a.ell_w = 0, 2, 1, 512, 0.5, 11
+        a.x, a.out, a.tape, a.qkv = 0x1000, 0x2000, 0x3000, 0x4000
+        a.dout, a.dx, a.gtape, a.wg_ws = 0x5000, 0x6000, 0x7000, 0x8000
+        for k, v in spoil.items():
+            setattr(a, k, v)
+        return a
+    both = [dict(level=3), dict(B=0), dict(B=2049), dict(cin0=256), dict(level=1, cin0=512), dict(ell_w=12), dict(p=1.0), dict(x=None)]
+    bwd_only = [dict(training=0), dict(dout=None)]
+    for suffix in ("", "_bf16", "_x3"):
+        fwd, bwd = getattr(c, "pdf_mesh_level_fwd" + suffix), getattr(c, "pdf_mesh_level_bwd" + suffix)
+        assert fwd(None, None) == -1 and bwd(None, None, None) == -1, suffix
+        for spoil in both:
+            assert fwd(ctypes.byref(block(**spoil)), None) == -1, (suffix, spoil)
+        for spoil in both + bwd_only:
+            assert bwd(ctypes.byref(block(**spoil)), None, None) == -1, (suffix, spoil)
+
+
 def test_bf16_storage_defaults_to_the_batches_where_it_wins(monkeypatch):
     """PDFNET_BF16_STORAGE unset = 'auto': bf16 storage of the conv -> BatchNorm tensors for convolutions over >= 32 images (B=64 per GPU:
     +2 %; B=32: +1.7 %, +3.8 % with the epilogue statistics since that step is GPU-bound (round 5); the launch-bound small batches lose),
