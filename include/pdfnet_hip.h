@@ -641,6 +641,41 @@ int pdf_mano_split_coeff(const float* params, int ldp, long HW, const long* ind,
 int pdf_mano_split_coeff_bwd(const float* params, float* dparams, int ldp, long HW, const long* ind, const float* K, int B, int input_res, int down,
                              const float* dorient, const float* dpose, const float* dtrans, void* stream);
 
+/* ---- MANO fit (csrc/manofit.hip) ---------------------------------------------------------------- */
+/* Row b: the MANO parameters whose mesh is closest to the target mesh of row b, by `iters` Levenberg-Marquardt trial steps.  Forward only.
+ * target [B,778,3] f32; valid [B] f32 or NULL; weight [B,778] f32 >= 0 or NULL (= 1; a negative weight counts as 0); init [B,61] f32 or NULL;
+ * v_template ... weights: the constants pdf_mano_lbs_fwd takes.
+ * Unknowns  p = [root 3 | pose 45 | shape 10 | trans 3], 61 floats.
+ * Model     M(p) = the vertices of pdf_mano_lbs_fwd(root, pose, shape, trans) with center_idx = -1: Rodrigues with angle = |a| + 1e-8; where
+ *           a = 0 the derivative of |a| is taken as 0, as pdf_mano_lbs_bwd does.
+ * Cost      E(p) = sum_v w_v |M(p)_v - t_v|^2 + prior_pose |pose|^2 + prior_shape |shape|^2.
+ * Start     init[b] when init is given; else root = pose = shape = 0 and trans = mean_v(t) - mean_v(v_template).
+ * Step      lambda = 1e-3 at the start.  With r = M(p) - t stacked to 2334 rows, J = dM / dp (2334 x 61, exact: it includes the pose blend
+ *           shapes and the dependence of the joints on the shape through J_reg) and prior = (0 x 3, prior_pose x 45, prior_shape x 10, 0 x 3):
+ *             A = J^T W J + diag(prior),   g = J^T W r + prior o p,
+ *             (A + lambda diag(max(A_ii, 1e-12))) delta = -g   by Cholesky;
+ *           if E(p + delta) < E(p): p <- p + delta, lambda <- max(lambda / 4, 1e-7); else p stays and lambda <- min(8 lambda, 1e6).  A pivot
+ *           that is not positive counts as a rejection.  Exactly `iters` trial steps are taken; there is no early exit.
+ * Outputs   params [B,61]; verts [B,778,3] = M(params) and joints [B,21,3], the 21 joints of pdf_mano_lbs_fwd at params (its order, its tip
+ *           vertices, `left_side` choosing 445 or 444); cost [B,2] = E at the start point and at params; info [B,2] int32 = accepted and
+ *           rejected steps (their sum is iters); lambda [B] = the damping after the last step.
+ *           A [B,61,61] and g [B,61], or NULL: the system of the last state at which one was built -- params itself when the last step was
+ *           rejected, the state before it when it was accepted; with iters = 0 the system is built once at the start point and no step is taken.
+ * A row with valid = 0 takes no step: params = the start point, verts / joints = its mesh, cost = 0, info = 0, lambda = 1e-3, A = g = 0.
+ * fp32 throughout, except that the sums over the 2334 rows are carried in double across tiles of 48 rows, the cost is summed in double, and the
+ * 61 x 61 factorisation and the two triangular solves run in double.  Every sum has a fixed order and no atomic is used: two runs are
+ * bit-identical and a row's result does not depend on the other rows of the batch.
+ * workspace: pdf_mano_fit_workspace_floats(B) floats of device memory for the row's Jacobian, or NULL when that is 0 -- as it is today: the
+ * kernel streams J through LDS in tiles of 16 vertices and spills nothing.  Callers allocate what the function returns.
+ * 0 <= iters <= 1000, the priors finite and >= 0, every pointer not called optional above not NULL, else PDF_E_BADARG with nothing launched;
+ * B <= 0 returns 0.  One launch, one workgroup per row, resident for the whole loop. */
+long pdf_mano_fit_workspace_floats(int B);
+int pdf_mano_fit(const float* target, const float* valid, const float* weight, const float* init,
+                 const float* v_template, const float* shapedirs, const float* posedirs, const float* J_reg, const float* weights,
+                 int B, int left_side, int iters, float prior_pose, float prior_shape,
+                 float* params, float* verts, float* joints, float* cost, int* info, float* lambda, float* A, float* g,
+                 float* workspace, void* stream);
+
 
 /* ---- explicit per-call options (round 4) ------------------------------------------------------------------------------
  * Everything a call can take beyond its positional arguments travels in ONE structure handed to the `_x` form of the entry

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpdfnet_hip.so")
 INCLUDE = os.path.join(HERE, "..", "include")        # pdfnet_hip.h: csrc/common.h includes it, so the compiler checks every definition against it
-SOURCES = ["gemm.hip", "gemm_dma.hip", "gemm_x3.hip", "winograd.hip", "gemm_bf16.hip", "pointops.hip", "norm.hip", "elementwise.hip", "graph.hip", "meshdec.hip", "meshdec_bf16.hip", "meshdec_x3.hip", "mano.hip", "frontend.hip", "loss.hip", "metrics.hip", "icp.hip", "meshcloud.hip", "penetration.hip", "silhouette.hip", "render.hip", "safused.hip"]
+SOURCES = ["gemm.hip", "gemm_dma.hip", "gemm_x3.hip", "winograd.hip", "gemm_bf16.hip", "pointops.hip", "norm.hip", "elementwise.hip", "graph.hip", "meshdec.hip", "meshdec_bf16.hip", "meshdec_x3.hip", "mano.hip", "manofit.hip", "frontend.hip", "loss.hip", "metrics.hip", "icp.hip", "meshcloud.hip", "penetration.hip", "silhouette.hip", "render.hip", "safused.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wno-unused-result", "-I" + INCLUDE]
 
 

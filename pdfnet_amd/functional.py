@@ -4,6 +4,7 @@ device memory, the current stream and the autograd tape; every computation below
 Activation layout: 4-D maps are logical NCHW tensors in torch.channels_last memory (physically NHWC,
 rows = pixels, channels contiguous); everything else is row-major [..., channels].
 """
+import collections
 import ctypes
 import torch
 from torch.autograd import Function
@@ -2136,6 +2137,57 @@ class _ManoLBS(Function):
 def mano_lbs(consts, root_aa, pose_aa, shape, trans=None, side='left', center_idx=None):
     """ManoLayer.forward (manolayer.py:257-334, use_pca=False), differentiable w.r.t. root / pose / shape / trans."""
     return _ManoLBS.apply(root_aa, pose_aa, shape, trans, consts, side == 'left', -1 if center_idx is None else int(center_idx))
+
+
+ManoFit = collections.namedtuple('ManoFit', 'root pose shape trans verts joints cost0 cost accepted rejected lam A g')
+MANO_FIT_MAX_ITERS = 1000
+
+
+def mano_fit(consts, target, side='left', valid=None, weight=None, init=None, iters=20, prior_pose=0.0, prior_shape=0.0, return_system=False):
+    """target [B, 778, 3] -> the MANO parameters whose mesh (`mano_lbs(consts, root, pose, shape, trans, side)`) is closest to it, by `iters`
+    Levenberg-Marquardt trial steps on E = sum_v w_v |M(p)_v - t_v|^2 + prior_pose |pose|^2 + prior_shape |shape|^2 from root = pose = shape = 0,
+    trans = mean(target) - mean(v_template), or from init [B, 61] = [root 3 | pose 45 | shape 10 | trans 3].  valid [B] or None: a row with
+    valid == 0 takes no step and has zero costs; weight [B, 778] >= 0 or None (= 1).
+    -> ManoFit(root [B, 3], pose [B, 45], shape [B, 10], trans [B, 3], verts [B, 778, 3], joints [B, 21, 3] of the fitted hand, cost0 / cost [B]
+    = E at the start and at the end, accepted / rejected int32 [B] steps, lam [B] the last damping, A [B, 61, 61] / g [B, 61] with return_system
+    (the normal equations of the last state at which they were built; iters = 0 builds them at the start point), else None).
+    The contract is `pdf_mano_fit`'s in pdfnet_hip.h.  One launch; no gradient; deterministic."""
+    hip.require_gpu(target, valid, weight, init, *(consts[k] for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'weights')))
+    if side not in ('left', 'right'):
+        raise ValueError("pdfnet_amd: mano_fit takes side 'left' or 'right', got %r" % (side,))
+    t = target.detach().float().contiguous()
+    if t.dim() != 3 or t.shape[1:] != (778, 3):
+        raise ValueError("pdfnet_amd: mano_fit wants target [B, 778, 3], got %s" % (tuple(t.shape),))
+    B, dev = t.shape[0], t.device
+    opt = []
+    for name, x, shape in (('valid', valid, (B,)), ('weight', weight, (B, 778)), ('init', init, (B, 61))):
+        if x is not None:
+            x = x.detach().float().contiguous()
+            if tuple(x.shape) != shape:
+                raise ValueError("pdfnet_amd: mano_fit wants %s %s, got %s" % (name, shape, tuple(x.shape)))
+        opt.append(x)
+    va, w, p0 = opt
+    for k, shape in (('v_template', (778, 3)), ('shapedirs', (778, 3, 10)), ('posedirs', (778, 3, 135)), ('J_regressor', (16, 778)), ('weights', (778, 16))):
+        c = consts[k]
+        if tuple(c.shape) != shape or c.dtype != torch.float32 or not c.is_contiguous():
+            raise ValueError("pdfnet_amd: mano_fit wants consts[%r] contiguous float32 %s, got %s %s" % (k, shape, c.dtype, tuple(c.shape)))
+    iters, prior_pose, prior_shape = int(iters), float(prior_pose), float(prior_shape)
+    if not 0 <= iters <= MANO_FIT_MAX_ITERS:
+        raise ValueError("pdfnet_amd: mano_fit takes 0 to %d iterations, got %r" % (MANO_FIT_MAX_ITERS, iters))
+    if not (0.0 <= prior_pose < float('inf') and 0.0 <= prior_shape < float('inf')):
+        raise ValueError("pdfnet_amd: mano_fit takes finite priors >= 0, got %r and %r" % (prior_pose, prior_shape))
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    params, verts, joints, cost, lam = f32(B, 61), f32(B, 778, 3), f32(B, 21, 3), f32(B, 2), f32(B)
+    info = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    A, g = (f32(B, 61, 61), f32(B, 61)) if return_system else (None, None)
+    L = _L()
+    nws = L.pdf_mano_fit_workspace_floats(B)
+    ws = _ws(nws, dev) if nws > 0 else None
+    L.pdf_mano_fit(ptr(t), ptr(va), ptr(w), ptr(p0), ptr(consts['v_template']), ptr(consts['shapedirs']), ptr(consts['posedirs']),
+                   ptr(consts['J_regressor']), ptr(consts['weights']), B, int(side == 'left'), iters, prior_pose, prior_shape,
+                   ptr(params), ptr(verts), ptr(joints), ptr(cost), ptr(info), ptr(lam), ptr(A), ptr(g), ptr(ws), stream())
+    return ManoFit(params[:, :3], params[:, 3:48], params[:, 48:58], params[:, 58:], verts, joints, cost[:, 0], cost[:, 1],
+                   info[:, 0], info[:, 1], lam, A, g)
 
 
 class _ManoSplitCoeff(Function):

@@ -625,7 +625,7 @@ class Trainer:
 
 
     def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False, rendered=False, refined=False,
-                   two_sided=False):
+                   two_sided=False, mano_fit=False):
         """Counterpart of `BaseTrainer.evaluation` (lib/trains/base_trainer.py:207-429, H2O branch): the test-mode pass
         (centres from the predicted heat-map, root from the predicted depth) and the mean Euclidean errors per hand --
         absolute and root-relative joints / vertices in mm, 2-D landmarks in pixels.  The reference evaluates on rank 0
@@ -656,7 +656,11 @@ class Trainer:
         two_sided:  also the trimmed, occlusion-aware Chamfer distance between the absolute meshes and the sensor point cloud batch['cloud']:
                     cloud to mesh (`F.mesh_icp` with iters = 0) and mesh to cloud over the vertices the camera sees (`F.mesh_cloud_loss`), for
                     the prediction and, as the sensor's own floor, for the ground truth -- the keys of `finish_two_sided`.  One more
-                    accumulator in the same buffer; needs `faces_pair`.  The other keys do not change."""
+                    accumulator in the same buffer; needs `faces_pair`.  The other keys do not change.
+        mano_fit:   False, or `load_mano_constants`' lbs_consts ({'left' / 'right': the constants `F.mano_lbs` takes}): also how far the meshes
+                    are from the space of MANO hands -- every valid predicted and ground-truth absolute mesh is fitted by `F.mano_fit`
+                    (MANO_FIT_ITERS Levenberg-Marquardt steps, one launch per hand and mesh set): the keys of `finish_mano_fit`.  One more
+                    accumulator in the same buffer.  The other keys do not change."""
         if refined not in (False, True, 'translation', 'rigid'):
             raise ValueError("Trainer.evaluation: refined is False, True, 'translation' or 'rigid', got %r" % (refined,))
         mwl = self.model_with_loss
@@ -678,6 +682,8 @@ class Trainer:
                 acc5 = torch.zeros(REFINED_SUMS, dtype=torch.float64, device=dev)      # see refined_sums
             if two_sided:
                 acc6 = torch.zeros(TWO_SIDED_SUMS, dtype=torch.float64, device=dev)    # see two_sided_sums
+            if mano_fit:
+                acc7 = torch.zeros(MANO_FIT_SUMS, dtype=torch.float64, device=dev)     # see mano_fit_sums
             poses = []
             with torch.no_grad():
                 for batch in loader:
@@ -696,6 +702,8 @@ class Trainer:
                         acc5 += refined_sums(tup, batch, mwl.loss.faces_pair, refined == 'rigid')
                     if two_sided:
                         acc6 += two_sided_sums(tup, batch, mwl.loss.faces_pair)
+                    if mano_fit:
+                        acc7 += mano_fit_sums(tup, batch, mano_fit)
                     if json_path is not None:
                         if 'id' not in batch or 'frame_num' not in batch:
                             raise KeyError("Trainer.evaluation: hand_poses.json needs batch['id'] and batch['frame_num'] (interhand.py H2O entries)")
@@ -705,6 +713,9 @@ class Trainer:
                         poses.append(torch.cat((key, jp.reshape(jp.shape[0], -1).double()), 1))          # [B, 2 + 126]
             if aligned:                                            # one buffer for the reduction and the copy (the counts are exact in float64)
                 acc = torch.cat((acc, acc2, pck.reshape(-1).double()))
+            if mano_fit:                                           # before the two-sided block
+                mt = acc.numel()
+                acc = torch.cat((acc, acc7))
             if two_sided:                                          # before the refined block
                 tt = acc.numel()
                 acc = torch.cat((acc, acc6))
@@ -730,6 +741,8 @@ class Trainer:
                 out.update(finish_refined(acc[rt:rt + REFINED_SUMS]))
             if two_sided:
                 out.update(finish_two_sided(acc[tt:tt + TWO_SIDED_SUMS]))
+            if mano_fit:
+                out.update(finish_mano_fit(acc[mt:mt + MANO_FIT_SUMS]))
             if json_path is not None:
                 rows = torch.cat(poses) if poses else torch.zeros((0, 128), dtype=torch.float64, device=dev)
                 if self.world > 1:                                 # ragged gather: pad every rank's block to the longest
@@ -1087,6 +1100,62 @@ def write_two_sided_scores(path, ev):
     with open(path, 'a') as fo:
         fo.write('eval two-sided \n')
         for k in TWO_SIDED_KEYS:
+            if k in ev:
+                fo.write('%s: %.2f\n' % (k, ev[k]))
+
+
+MANO_FIT_NAMES = ('mano_residual', 'mano_residual_gt', 'mano_abs_verts', 'mano_abs_joints')
+MANO_FIT_KEYS = tuple(n + e for n in MANO_FIT_NAMES for e in ('_left', '_right', '')) + ('mano_fit_samples',)
+MANO_FIT_SUMS = 11
+MANO_FIT_ITERS = 20                          # Levenberg-Marquardt trial steps of the evaluation's MANO fit
+
+
+def mano_fit_sums(tup, batch, lbs_consts):
+    """test-mode 9-tuple, the batch (`valid` [B, 2]) and `load_mano_constants`' lbs_consts -> float64 [11] on the device.  The predicted and the
+    ground-truth absolute meshes are fitted by `mano_fit_pair` (MANO_FIT_ITERS steps from the default start).  [0] the number of samples; then,
+    per quantity, the pair (left, right) of sums over the samples with that hand valid (valid == 1) of the per-sample mean distance: [1:3]
+    predicted mesh to its fit, [3:5] ground-truth mesh to its fit, [5:7] the prediction's fitted vertices and [7:9] its fitted joints to the
+    ground truth; [9:11] the number of such samples."""
+    from ..utils import mano_fit_pair
+    vp, _, vg, jg = tup[:4]
+    valid = batch['valid']
+    fp = mano_fit_pair(lbs_consts, vp, valid, iters=MANO_FIT_ITERS)
+    fg = mano_fit_pair(lbs_consts, vg, valid, iters=MANO_FIT_ITERS)
+    pv, pj, gv = (torch.stack((a, b), 1) for a, b in ((fp[0].verts, fp[1].verts), (fp[0].joints, fp[1].joints), (fg[0].verts, fg[1].verts)))
+    has = valid == 1                                                                             # [B, 2]
+    terms = torch.stack((F.point_dist_sum(vp, pv).double() / vp.shape[-2], F.point_dist_sum(vg, gv).double() / vp.shape[-2],
+                         F.point_dist_sum(pv, vg).double() / vp.shape[-2], F.point_dist_sum(pj, jg).double() / jg.shape[-2],
+                         torch.ones(has.shape, dtype=torch.float64, device=vp.device)))         # [5, B, 2]
+    n = torch.full((1,), float(vp.shape[0]), dtype=torch.float64, device=vp.device)
+    return torch.cat((n, torch.where(has, terms, torch.zeros_like(terms)).sum(1).reshape(-1)))
+
+
+def finish_mano_fit(acc):
+    """The accumulator of `mano_fit_sums` -> in mm, each as '<key>_left', '<key>_right' (means over the samples with that hand valid) and
+    '<key>' (the mean of the two hands, or the one there is): 'mano_residual' (mean distance between the predicted absolute mesh and its MANO
+    fit: how far from a hand the prediction is), 'mano_residual_gt' (the same for the ground-truth mesh: the floor), 'mano_abs_verts' /
+    'mano_abs_joints' (the fitted mesh and its joints against the ground truth, to sit beside `abs_*`); 'mano_fit_samples'.  A mean over
+    nothing is 0; without a sample only 'mano_fit_samples'."""
+    a = [float(x) for x in acc]
+    out = {'mano_fit_samples': int(round(a[0]))}
+    if out['mano_fit_samples'] == 0:
+        return out
+    for i, name in enumerate(MANO_FIT_NAMES):
+        there = []
+        for h, hand in enumerate(('left', 'right')):
+            n = round(a[9 + h])
+            out['%s_%s' % (name, hand)] = a[1 + 2 * i + h] / a[9 + h] * 1000 if n > 0 else 0.0
+            if n > 0:
+                there.append(out['%s_%s' % (name, hand)])
+        out[name] = sum(there) / len(there) if there else 0.0
+    return {k: out[k] for k in MANO_FIT_KEYS}
+
+
+def write_mano_fit_scores(path, ev):
+    """Append the figures of `evaluation(mano_fit=...)` that are there as a block of their own (`key: %.2f`, like `write_two_sided_scores`)."""
+    with open(path, 'a') as fo:
+        fo.write('eval mano-fit \n')
+        for k in MANO_FIT_KEYS:
             if k in ev:
                 fo.write('%s: %.2f\n' % (k, ev[k]))
 

@@ -84,6 +84,21 @@ def mano_from_params(mano_consts, params_map, ind, K, input_res, down_ratio=4):
     return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out]), trans
 
 
+def mano_fit_pair(lbs_consts, verts, valid=None, **kw):
+    """verts [B, 2, 778, 3] (left, right hand, absolute metres), valid [B, 2] or None -> (left, right): `F.mano_fit` of each hand with its own
+    constants (`load_mano_constants`' lbs_consts); **kw goes to `F.mano_fit` (iters, priors, return_system; weight / init as [B, 2, ...])."""
+    if verts.dim() != 4 or verts.shape[1:] != (2, 778, 3):
+        raise ValueError("pdfnet_amd: mano_fit_pair wants verts [B, 2, 778, 3], got %s" % (tuple(verts.shape),))
+    if valid is not None and tuple(valid.shape) != (verts.shape[0], 2):
+        raise ValueError("pdfnet_amd: mano_fit_pair wants valid %s, got %s" % ((verts.shape[0], 2), tuple(valid.shape)))
+    per_hand = {k: kw.pop(k) for k in ('weight', 'init') if kw.get(k) is not None}
+    out = []
+    for h, side in enumerate(('left', 'right')):
+        out.append(F.mano_fit(lbs_consts[side], verts[:, h], side=side, valid=None if valid is None else valid[:, h],
+                              **{k: v[:, h] for k, v in per_hand.items()}, **kw))
+    return tuple(out)
+
+
 def load_mano_constants(npz_path, device=None):
     """`mano_constants.npz` (written at the user's site by tools/convert_mano.py from MANO_LEFT.pkl / MANO_RIGHT.pkl) ->
     (loss_consts, lbs_consts): what the reference builds in `ManoLayer.__init__` (lib/models/networks/manolayer.py:100-160),
