@@ -703,12 +703,17 @@ int pdf_mano_fit(const float* target, const float* valid, const float* weight, c
  *                        error on values of a few units -- where the map edges are multiples of 4 and PDF_WINOGRAD_F4 (bit mask, default 15 = every
  *                        launch) permits, else F(2x2, 3x3) (16 planes, 2.25x fewer, MORE accurate than the direct fp32 sum); the weight gradient is
  *                        taken in the transform domain too (backward = 2).  PDF_WINOGRAD=2: F(2x2) only; =0: the direct kernels.
+ *                        The library plans such a launch once per call (form, plane format, where each buffer lies in `ws`) and runs it only when
+ *                        ws_floats covers the plan's total; with less -- or an unaligned ws -- the call runs the direct kernels.  The same holds
+ *                        for the x3 transposed convolutions (pdf_deconv2d_x3_workspace_floats).  pdf_debug_workspace_plan returns a plan as numbers.
  *   wino_v               pdf_conv2d_bwd_weight (Winograd F(4x4) path): the transformed input V [36][tiles][Cin] that the FORWARD of the same
  *                        convolution left in its workspace (at float offset pdf_conv2d_winograd_v_offset(...) of the forward `ws`): the
  *                        weight gradient then skips its own input transform (same kernel, same values).  The caller keeps that workspace
  *                        alive and unmodified from the forward to the weight-gradient call.
  *                        pdf_conv2d_fwd (F(4x4) launches): V of the SAME input tensor from another convolution's forward workspace (several
- *                        heads reading one feature map): this forward skips its input transform.  V depends on (x, N, H, W, Cin) only.
+ *                        heads reading one feature map): this forward skips its input transform.  V depends on (x, N, H, W, Cin) only,
+ *                        and so does its format (fp32 or x3 planes): each plan records the format a V handed to it has and the format its own
+ *                        products read, and a launch whose two differ ignores wino_v and transforms the input itself.
  */
 typedef struct PdfCallOpts {
     const void* op0_bf16; const void* op1_bf16;      /* bf16 shadows of the call's two operands (GEMM family) */
@@ -775,6 +780,16 @@ int pdf_set_x3_mode(int mode);
 /* a HIP stream of the given priority (clamped to the device's range, returned in *lo (least) / *hi (greatest) when not NULL; out == NULL: only the range) */
 int pdf_stream_create(void** out, int priority, int* lo, int* hi);
 int pdf_debug_x3_mode(void);
+/* The workspace plan of one launch as numbers, computed on the host (no device needed): kind 0 = the Winograd path of a stride-1 3x3 convolution,
+ * 1 = the x3 form of a transposed convolution; pass 0 / 1 / 2 = forward / backward-data / weight gradient; the shape as in the size queries.
+ *   out[0] ok (0: the layer does not take the path; then total = 0 and no regions)    out[1] total floats (= the size query's result)
+ *   out[2] form: Winograd tile edge m (4 | 2), x3 deconv 0 = kernel == stride / 1 = general    out[3] 1 when the operand planes are x3
+ *   out[4] splits of the weight gradient's reduction (0: none planned)    out[5] Winograd forward: pdf_conv2d_winograd_v_offset, else -1
+ *   out[6] Winograd: format (0 fp32 / 1 x3) of a V handed in through PdfCallOpts::wino_v, used only when == out[3]; -1: none can exist
+ *   out[7] number of regions R, then R pairs (float offset, floats) -- Winograd forward / backward-data: U, V, M; weight gradient: V, Yh, slabs,
+ *          column-sum scratch; x3 deconv: first operand, second operand (, slabs).
+ * Returns the count of values of the plan; at most `cap` are written. */
+int pdf_debug_workspace_plan(int kind, int pass, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, long* out, int cap);
 int pdf_debug_x3_stamps(unsigned long long* out);       /* diagnostic builds (-DX3_STAMPS=1) only: phase clocks of block 0 of the last x3gemm_nt launch; 0 otherwise */
 int pdf_x3_batched_gemm_nt(const void* A3, long csA, const void* B3, long csB, float* C, int batch, long gsA, long gsB, long gsC, int M, int N, int K, int variant, int nprod, void* stream);
 int pdf_batched_gemm_nt(const float* A, const float* B, float* C, int batch, long gsA, long gsB, long gsC, int M, int N, int K, void* stream);

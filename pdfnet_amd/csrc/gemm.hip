@@ -14,18 +14,6 @@
 #include "gemm_common.h"
 #include "gemm_internal.h"
 
-// Workspace (floats) a stride-1 3x3 convolution [Cout][3][3][Cin] on N x H x W maps wants for its Winograd path -- backward = 0: the
-// forward pass, 1: backward-data, 2: the weight gradient -- or 0 when the layer does not qualify (then no workspace is needed)
-PDF_API long pdf_conv2d_winograd_v_offset(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-    if (!pdf_internal_wino_eligible(N, H, W, Cin, Cout, KH, KW, stride, pad, 0) || !pdf_internal_wino_wgrad_eligible(N, H, W, Cin, Cout, KH, KW, stride, pad)) return -1;
-    return pdf_internal_wino_v_offset(N, H, W, Cin, Cout);
-}
-PDF_API long pdf_conv2d_winograd_workspace_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int backward) {
-    if (backward == 2) return pdf_internal_wino_wgrad_eligible(N, H, W, Cin, Cout, KH, KW, stride, pad) ? pdf_internal_wino_wgrad_workspace(N, H, W, Cin, Cout) : 0;
-    const int Ck = backward ? Cout : Cin, Cn = backward ? Cin : Cout;
-    return pdf_internal_wino_eligible(N, H, W, Ck, Cn, KH, KW, stride, pad, backward) ? pdf_internal_wino_workspace(N, H, W, Ck, Cn, backward) : 0;
-}
-
 constexpr int WG_ISSUE_AT = 1;                  // wgemm_tn_dma, scalar-offset form: the k-pair after which the next tile's loads are issued
 // (Measured and rejected: ds_read_b128 fragments over a [BK + 4] image and fragment reads pipelined one k-pair ahead -- profiles/r05_ig_b128.txt.)
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
@@ -1485,9 +1473,6 @@ int pdf_internal_batched_gemm(const float* A, const float* B, float* C, int batc
     return launch_igemm(g, s, batch);
 }
 
-PDF_API long pdf_deconv2d_x3_workspace_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int backward) {
-    return g_gemm_bf16 ? 0 : pdf_internal_x3_deconv_workspace(N, H, W, Cin, Cout, KH, KW, stride, pad, backward);
-}
 static void conv_taps(IGemm& g, int KH, int KW, int pad, int dil) {
     g.T = KH * KW;
     for (int ky = 0; ky < KH; ++ky)
@@ -1825,12 +1810,13 @@ static int pdf_conv2d_fwd_impl(const float* x, const float* w, const float* bias
         PDF_LAUNCH_CHECK();
         return 0;
     }
-    // Winograd F(4x4, 3x3) / F(2x2, 3x3) (winograd.hip: pdf_internal_wino_tile picks): fp32 mode, the caller handed a workspace (PdfCallOpts::ws), the layer qualifies
-    if (!g_gemm_bf16 && co.ws != nullptr && y16 == nullptr && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(co.ws) &&
-        pdf_internal_wino_eligible(N, H, W, Cin, Cout, KH, KW, stride, pad, 0) && co.ws_floats >= pdf_internal_wino_workspace(N, H, W, Cin, Cout, 0)) {
-        g_last_tile = 128128;
-        return pdf_internal_conv3x3_winograd(x, ldx, w, bias, y, ldy, co.ws, N, H, W, Cin, Cout, act, 0, 0,
-                                             (co.wino_v != nullptr && aligned16(co.wino_v) && pdf_internal_wino_v_offset(N, H, W, Cin, Cout) >= 0) ? co.wino_v : nullptr, s);
+    // Winograd F(4x4, 3x3) / F(2x2, 3x3) (winograd.hip: wino_plan decides): fp32 mode, the caller handed a workspace (PdfCallOpts::ws), the layer qualifies
+    if (!g_gemm_bf16 && co.ws != nullptr && y16 == nullptr && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(co.ws)) {
+        const WinoPlan plan = wino_plan(N, H, W, Cin, Cout, KH, KW, stride, pad, 0);
+        if (plan.ok && co.ws_floats >= plan.total) {
+            g_last_tile = 128128;
+            return pdf_internal_conv3x3_winograd(plan, x, ldx, w, bias, y, ldy, co.ws, act, 0, aligned16(co.wino_v) ? co.wino_v : nullptr, s);
+        }
     }
     IGemm g = {};
     g.A = x; g.B = w; g.C = y; g.bias = bias;
@@ -1865,10 +1851,12 @@ static int pdf_conv2d_bwd_data_impl(const float* dy, const float* w, float* dx,
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
     if (accumulate && stride > 1) return PDF_E_BADARG;       // (every dx element must be written by exactly one launch)
     // Winograd: dx = the 3x3 convolution of dy (Cout channels) with the mirrored taps, Cin output channels
-    if (!g_gemm_bf16 && co.ws != nullptr && lddx % 4 == 0 && lddy % 4 == 0 && aligned16(dy) && aligned16(dx) && aligned16(co.ws) && OH == H && OW == W &&
-        pdf_internal_wino_eligible(N, H, W, Cout, Cin, KH, KW, stride, pad, 1) && co.ws_floats >= pdf_internal_wino_workspace(N, H, W, Cout, Cin, 1)) {
-        g_last_tile = 128128;
-        return pdf_internal_conv3x3_winograd(dy, lddy, w, nullptr, dx, lddx, co.ws, N, H, W, Cout, Cin, 0, accumulate, 1, nullptr, s);
+    if (!g_gemm_bf16 && co.ws != nullptr && lddx % 4 == 0 && lddy % 4 == 0 && aligned16(dy) && aligned16(dx) && aligned16(co.ws) && OH == H && OW == W) {
+        const WinoPlan plan = wino_plan(N, H, W, Cout, Cin, KH, KW, stride, pad, 1);
+        if (plan.ok && co.ws_floats >= plan.total) {
+            g_last_tile = 128128;
+            return pdf_internal_conv3x3_winograd(plan, dy, lddy, w, nullptr, dx, lddx, co.ws, 0, accumulate, nullptr, s);
+        }
     }
     for (int py = 0; py < stride; ++py)
         for (int px = 0; px < stride; ++px) {
@@ -1883,19 +1871,7 @@ static int pdf_conv2d_bwd_data_impl(const float* dy, const float* w, float* dx,
             g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
             g.B16T = co.op1_bf16_t; g.ldbT = KH * KW * Cout;
             // input row iy = qy*stride + py; contributing taps: (iy + pad - ky) % stride == 0, oy = (iy+pad-ky)/stride
-            int T = 0;
-            for (int ky = 0; ky < KH; ++ky) {
-                if ((py + pad - ky) % stride != 0) continue;
-                for (int kx = 0; kx < KW; ++kx) {
-                    if ((px + pad - kx) % stride != 0) continue;
-                    // oy = qy + (py + pad - ky)/stride  (exact division, may be negative)
-                    int ny = py + pad - ky, nx = px + pad - kx;
-                    g.dy[T] = (int)(ny >= 0 ? ny / stride : -((-ny) / stride));
-                    g.dx[T] = (int)(nx >= 0 ? nx / stride : -((-nx) / stride));
-                    g.wt[T] = (int)(ky * KW + kx);
-                    ++T;
-                }
-            }
+            const int T = pdf_parity_taps(KH, KW, stride, pad, py, px, g.dy, g.dx, g.wt);      // oy = qy + g.dy[t]
             if (T == 0) continue;
             g.T = T; g.K = T * Cout;
             g.plain_in = 0; g.plain_out = 0;
@@ -2225,10 +2201,11 @@ static int pdf_conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
     // Winograd F(4x4, 3x3) weight gradient (winograd.hip): fp32 mode, the caller handed a workspace (PdfCallOpts::ws), the layer qualifies
     if (!g_gemm_bf16 && co.ws != nullptr && dy != nullptr && OH == H && OW == W && ldx % 4 == 0 && lddy % 4 == 0 && aligned16(x) && aligned16(dy) &&
-        aligned16(co.ws) && pdf_internal_wino_wgrad_eligible(N, H, W, Cin, Cout, KH, KW, stride, pad) &&
-        co.ws_floats >= pdf_internal_wino_wgrad_workspace(N, H, W, Cin, Cout))
-        return pdf_internal_conv3x3_winograd_wgrad(x, ldx, dy, lddy, dw, db, co.ws, N, H, W, Cin, Cout, accumulate,
-                                                   (co.wino_v != nullptr && aligned16(co.wino_v) && pdf_internal_wino_v_offset(N, H, W, Cin, Cout) >= 0) ? co.wino_v : nullptr, s);
+        aligned16(co.ws)) {
+        const WinoWgradPlan plan = wino_wgrad_plan(N, H, W, Cin, Cout, KH, KW, stride, pad);
+        if (plan.ok && co.ws_floats >= plan.total)
+            return pdf_internal_conv3x3_winograd_wgrad(plan, x, ldx, dy, lddy, dw, db, co.ws, accumulate, aligned16(co.wino_v) ? co.wino_v : nullptr, s);
+    }
     // bf16 storage mode: dy exists only as bf16 (dy == NULL) -- the launch must be one the bf16 kernel takes with a shadow operand
     if (dy == nullptr && (co.op1_bf16 == nullptr || db != nullptr || !g_gemm_bf16 || Cin % 16 != 0 || Cout % 16 != 0 || lddy % 8 != 0)) return PDF_E_BADARG;
     if (Cin == 3 && Cout == 3 && KH == 3 && KW == 3 && stride == 1 && db == nullptr && (long)N * OH * OW >= (1L << 16) && ws_floats >= 81L * 64) {
@@ -2307,12 +2284,9 @@ static int pdf_deconv2d_fwd_impl(const float* x, const float* w, const float* bi
                              int stride, int pad, int OH, int OW, int ldy, void* stream, PdfCallOpts& co) {
     hipStream_t s = (hipStream_t)stream;
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
-    if (!g_gemm_bf16 && co.ws != nullptr && ldx == Cin && ldy == Cout) {  // x3 form (gemm_x3.hip): kernel == stride, long reduction, workspace handed in
-        const long need = pdf_internal_x3_deconv_workspace(N, H, W, Cin, Cout, KH, KW, stride, pad, 0);
-        if (need > 0 && co.ws_floats >= need && ((uintptr_t)co.ws & 15) == 0) {
-            if (KH != stride || pad != 0) return pdf_internal_x3_deconv_general_fwd(x, w, bias, y, co.ws, N, H, W, Cin, Cout, KH, stride, pad, OH, OW, ldy, s);
-            return pdf_internal_x3_deconv_fwd(x, w, bias, y, co.ws, N, H, W, Cin, Cout, KH, KW, stride, OH, OW, ldy, s);
-        }
+    if (!g_gemm_bf16 && co.ws != nullptr && ldx == Cin && ldy == Cout && aligned16(co.ws)) {  // x3 form (gemm_x3.hip): long reduction, workspace handed in
+        const X3DeconvPlan plan = x3_deconv_plan(N, H, W, Cin, Cout, KH, KW, stride, pad, 0);
+        if (plan.ok && OH == plan.OH && OW == plan.OW && co.ws_floats >= plan.total) return pdf_internal_x3_deconv_fwd(plan, x, w, bias, y, co.ws, ldy, s);
     }
     if (KH == stride && KW == stride && pad == 0) {
         IGemm g = {};
@@ -2336,18 +2310,7 @@ static int pdf_deconv2d_fwd_impl(const float* x, const float* w, const float* bi
             if (g.QH <= 0 || g.QW <= 0) continue;
             g.M = N * g.QH * g.QW;
             g.sy = 1; g.sx = 1;
-            int T = 0;
-            for (int ky = 0; ky < KH; ++ky) {
-                if ((py + pad - ky) % stride != 0) continue;
-                for (int kx = 0; kx < KW; ++kx) {
-                    if ((px + pad - kx) % stride != 0) continue;
-                    int ny = py + pad - ky, nx = px + pad - kx;      // iy = qy + ny/stride
-                    g.dy[T] = (int)(ny >= 0 ? ny / stride : -((-ny) / stride));
-                    g.dx[T] = (int)(nx >= 0 ? nx / stride : -((-nx) / stride));
-                    g.wt[T] = (int)(ky * KW + kx);
-                    ++T;
-                }
-            }
+            const int T = pdf_parity_taps(KH, KW, stride, pad, py, px, g.dy, g.dx, g.wt);      // iy = qy + g.dy[t]
             if (T == 0) return PDF_E_BADARG;      // would need a bias-only fill; not used by PDFNet
             g.T = T; g.K = T * Cin;
             g.plain_in = 0; g.plain_out = 0;
@@ -2376,12 +2339,9 @@ static int pdf_deconv2d_bwd_data_impl(const float* dy, const float* w, float* dx
                                   int stride, int pad, int OH, int OW, int lddy, void* stream, PdfCallOpts& co) {
     hipStream_t s = (hipStream_t)stream;
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
-    if (!g_gemm_bf16 && co.ws != nullptr && lddy == Cout && lddx >= Cin) {
-        const long need = pdf_internal_x3_deconv_workspace(N, H, W, Cin, Cout, KH, KW, stride, pad, 1);
-        if (need > 0 && co.ws_floats >= need && ((uintptr_t)co.ws & 15) == 0) {
-            if (KH != stride || pad != 0) return pdf_internal_x3_deconv_general_bwd_data(dy, w, dx, co.ws, N, H, W, Cin, lddx, Cout, KH, stride, pad, OH, OW, lddy, s);
-            return pdf_internal_x3_deconv_bwd_data(dy, w, dx, co.ws, N, H, W, Cin, lddx, Cout, KH, KW, stride, OH, OW, lddy, s);
-        }
+    if (!g_gemm_bf16 && co.ws != nullptr && lddy == Cout && lddx >= Cin && aligned16(co.ws)) {
+        const X3DeconvPlan plan = x3_deconv_plan(N, H, W, Cin, Cout, KH, KW, stride, pad, 1);
+        if (plan.ok && OH == plan.OH && OW == plan.OW && co.ws_floats >= plan.total) return pdf_internal_x3_deconv_bwd_data(plan, dy, w, dx, co.ws, lddx, lddy, s);
     }
     IGemm g = {};
     g.A = dy; g.B = w; g.C = dx; g.bias = nullptr; g.A16 = co.op0_bf16; g.B16 = co.op1_bf16;
@@ -2409,12 +2369,9 @@ static int pdf_deconv2d_bwd_weight_impl(const float* x, const float* dy, float* 
                                     int stride, int pad, int OH, int OW, int lddy, int accumulate, void* stream, PdfCallOpts& co) {
     hipStream_t s = (hipStream_t)stream;
     if (KH * KW > MAX_TAPS) return PDF_E_BADARG;
-    if (!g_gemm_bf16 && co.ws != nullptr && ldx == Cin && lddy == Cout) {  // x3 form (gemm_x3.hip), workspace in PdfCallOpts::ws
-        const long need = pdf_internal_x3_deconv_workspace(N, H, W, Cin, Cout, KH, KW, stride, pad, 2);
-        if (need > 0 && co.ws_floats >= need && ((uintptr_t)co.ws & 15) == 0) {
-            if (KH != stride || pad != 0) return pdf_internal_x3_deconv_general_bwd_weight(x, dy, dw, co.ws, N, H, W, Cin, Cout, KH, stride, pad, OH, OW, lddy, accumulate, s);
-            return pdf_internal_x3_deconv_bwd_weight(x, dy, dw, co.ws, N, H, W, Cin, Cout, KH, KW, stride, OH, OW, lddy, accumulate, s);
-        }
+    if (!g_gemm_bf16 && co.ws != nullptr && ldx == Cin && lddy == Cout && aligned16(co.ws)) {  // x3 form (gemm_x3.hip), workspace in PdfCallOpts::ws
+        const X3DeconvPlan plan = x3_deconv_plan(N, H, W, Cin, Cout, KH, KW, stride, pad, 2);
+        if (plan.ok && OH == plan.OH && OW == plan.OW && co.ws_floats >= plan.total) return pdf_internal_x3_deconv_bwd_weight(plan, x, dy, dw, co.ws, lddy, accumulate, s);
     }
     WGemm g = {};
     g.P = x; g.Q = dy; g.P16 = co.op0_bf16; g.Q16 = co.op1_bf16; g.M = N * H * W; g.NI = Cin; g.Cq = Cout; g.T = KH * KW;

@@ -225,6 +225,21 @@ struct WGemm {
     int dy[MAX_TAPS], dx[MAX_TAPS], wt[MAX_TAPS];    // int, not short: a uniform index then compiles to s_load_dword; 16-bit entries become vector loads whose vmcnt(0) wait drains the prefetch
 };
 
+// Taps of parity class (py, px) of a stride-`stride` transposed convolution's output (equally: of a strided convolution's input, for its
+// backward-data): the (ky, kx) with (p + pad - k) % stride == 0, in (ky, kx) order.  dy / dx [t] = (p + pad - k) / stride, the tap's source
+// pixel relative to the class pixel (exact division, may be negative); wt[t] = ky * KW + kx.  -> the count (arrays of KH * KW entries hold them).
+static inline int pdf_parity_taps(int KH, int KW, int stride, int pad, int py, int px, int* dy, int* dx, int* wt) {
+    int T = 0;
+    for (int ky = 0; ky < KH; ++ky) {
+        if ((py + pad - ky) % stride != 0) continue;
+        for (int kx = 0; kx < KW; ++kx) {
+            if ((px + pad - kx) % stride != 0) continue;
+            dy[T] = (py + pad - ky) / stride; dx[T] = (px + pad - kx) / stride; wt[T] = ky * KW + kx;
+            ++T;
+        }
+    }
+    return T;
+}
 
 // a pointer that has the same value in every lane of the wave, as a scalar
 __device__ __forceinline__ float* wave_uniform(float* p) {

@@ -789,21 +789,74 @@ int pdf_internal_x3_mode() {
 }
 PDF_API int pdf_set_x3_mode(int mode) { g_x3_mode = mode < 0 ? -1 : (mode & 7); return 0; }
 PDF_API int pdf_debug_x3_mode(void) { return pdf_internal_x3_mode(); }
-static int x3_deconv_mode() { return (pdf_internal_x3_mode() & 2) != 0; }
 // row stride (elements) of a pre-split operand with K columns: one 128-byte line of padding, so that rows of 2^k bytes (p5: 4 KB and 32 KB) do not
 // all start on the same L2 / HBM channel (without it p5's backward-data ran 1.57 ms against 1.29 of the native kernel: profiles/r06_x3_deconv.txt)
 static long x3_ld(long K) { return K + 64; }
+// floats of workspace that hold n bf16 elements as three component planes (in 16-byte granules)
+static long x3_floats(long n) { return ((3 * n + 1) / 2 + 3) / 4 * 4; }
+// the next operand of a plan: `rows` rows of K columns (+ the zero row of a gathered operand); false when its planes leave 32-bit byte offsets
+static bool x3_carve(X3Operand& o, long& at, long rows, long K, int zrow) {
+    o.ld = x3_ld(K); o.cs = (rows + zrow) * o.ld; o.off = at; o.len = x3_floats(o.cs);
+    at += o.len;
+    return 3.0 * o.cs < 2147483000.0;
+}
+static int x3_general_wgrad_splits(long M, int NI, long NJ) {      // ~2 blocks per CU, at least 64 K-steps per block
+    const long tiles = (long)cdiv(NI, 128) * cdiv(NJ, 128);
+    long sp = (512 + tiles - 1) / tiles;
+    if (sp > M / 2048) sp = M / 2048;
+    return (int)(sp < 1 ? 1 : sp);
+}
+// The plan of a transposed convolution's x3 form (gemm_internal.h): which of the two forms, whether the layer qualifies, and the workspace layout.
+//   kernel == stride, pad 0 (p4, p5)        one plain GEMM over the input pixels + pixel shuffle; its weight gradient one x3gemm_tn launch;
+//   kernel a multiple of the stride (the pyramid's p3: 512 -> 256, k = 4, s = 2, pad = 1; intaghand_encoder.py:602):
+//     forward        s x s parity classes of output pixels, each an implicit GEMM over its (k / s)^2 taps: rows = the class's pixels (qy, qx), A = x at
+//                    (qy + dy[t], qx + dx[t]) (zero outside the map), B = the class's taps of w gathered and transposed by the pre-pass, output scattered
+//                    to (qy s + py, qx s + px);
+//     backward-data  ONE implicit GEMM: rows = input pixels (iy, ix), A = dy at (iy s - pad + ky, ix s - pad + kx) over all k^2 taps, B = w as it lies;
+//     weight gradient  x3gemm_tn with the dy operand gathered per tap, the reduction split into slabs.
+//   Same x3gemm_nt kernel (template IM): the tap's pixel offset is applied per lane when the tap changes, its channels advance by the scalar offset.
+// Both want a long reduction over a large product (>= 3e10 flops) and channel counts that are multiples of a K-step.
+X3DeconvPlan x3_deconv_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int pass) {
+    X3DeconvPlan p = {};
+    if (!(pdf_internal_x3_mode() & 2) || KH != KW || stride < 2 || Cin % 32 != 0 || Cout % 32 != 0) return p;
+    const int K = KH;
+    p.pass = pass; p.general = K != stride || pad != 0;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.K = K; p.stride = stride; p.pad = pad;
+    p.OH = (H - 1) * stride - 2 * pad + K; p.OW = (W - 1) * stride - 2 * pad + K;
+    const long Min = (long)N * H * W, Mout = (long)N * p.OH * p.OW, NT = (long)K * K * Cout;
+    bool fits;
+    if (!p.general) {
+        if (Min < 1024 || 2.0 * Min * NT * Cin < 3.0e10) return p;      // (p4, p5)
+        if (pass == 2 && (Min % 32 != 0 || 3.0 * Cin * NT * 4.0 >= 4294967000.0)) return p;
+        fits = pass == 2 ? x3_carve(p.w, p.total, Min, Cin, 0) : pass ? x3_carve(p.w, p.total, Cin, NT, 0) : x3_carve(p.w, p.total, NT, Cin, 0);
+        fits &= pass ? x3_carve(p.a, p.total, Min, NT, 0) : x3_carve(p.a, p.total, Min, Cin, 0);      // (backward passes: dy unshuffled to [pixel][(tap, co)])
+    } else {
+        if (K % stride != 0 || K * K > 16 || K <= stride || pad < 0 || pad >= K || p.OH % stride != 0 || p.OW % stride != 0) return p;
+        if (2.0 * Min * K * K * Cin * Cout < 3.0e10) return p;
+        if (pass == 2) {                                     // P = x, Q = dy (+ zero row), slabs of the split reduction
+            if ((H & (H - 1)) || (W & (W - 1)) || Min % 32 != 0 || Cout % 128 != 0) return p;
+            fits = x3_carve(p.w, p.total, Min, Cin, 0);
+            fits &= x3_carve(p.a, p.total, Mout, Cout, 1);
+            p.splits = x3_general_wgrad_splits(Min, Cin, NT);
+            p.slab = {p.total, (long)p.splits * Cin * NT};
+            p.total += p.slab.len;
+        } else if (pass == 0) {                              // B = the taps of w per parity class, A = x (+ zero row)
+            const long T = (long)(K / stride) * (K / stride);
+            fits = x3_carve(p.w, p.total, (long)stride * stride * Cout, T * Cin, 0);
+            fits &= x3_carve(p.a, p.total, Min, Cin, 1);
+        } else {                                             // B = w as it lies, A = dy (+ zero row)
+            fits = x3_carve(p.w, p.total, Cin, NT, 0);
+            fits &= x3_carve(p.a, p.total, Mout, Cout, 1);
+        }
+    }
+    p.total += 64;
+    if (!fits) { p = X3DeconvPlan{}; return p; }
+    p.ok = 1;
+    return p;
+}
 // floats of workspace the x3 form of this transposed convolution wants (backward = 0: forward, 1: backward-data, 2: weight gradient), 0 when it does not qualify
-static long x3_deconv_general_workspace(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad, int backward);
-long pdf_internal_x3_deconv_workspace(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int backward) {
-    if (!x3_deconv_mode() || KH != KW || stride < 2) return 0;
-    if (KH != stride || pad != 0) return x3_deconv_general_workspace(N, H, W, Cin, Cout, KH, stride, pad, backward);
-    const long M = (long)N * H * W, NT = (long)KH * KW * Cout;
-    if (Cin % 32 != 0 || Cout % 32 != 0 || M < 1024 || 2.0 * M * NT * Cin < 3.0e10) return 0;      // (a long reduction over a large product: p4, p5)
-    if (backward == 2 && (M % 32 != 0 || 3.0 * Cin * NT * 4.0 >= 4294967000.0)) return 0;
-    const long wel = backward == 2 ? M * x3_ld(Cin) : backward ? Cin * x3_ld(NT) : NT * x3_ld(Cin), ael = backward ? M * x3_ld(NT) : M * x3_ld(Cin);
-    if (3.0 * wel >= 2147483000.0 || 3.0 * ael >= 2147483000.0) return 0;
-    return ((3 * wel + 1) / 2 + 3) / 4 * 4 + ((3 * ael + 1) / 2 + 3) / 4 * 4 + 64;
+PDF_API long pdf_deconv2d_x3_workspace_floats(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int backward) {
+    return pdf_debug_gemm_precision() ? 0 : x3_deconv_plan(N, H, W, Cin, Cout, KH, KW, stride, pad, backward).total;
 }
 static void x3_gemm_desc(X3Gemm& g, const void* A3, long csA, long lda, const void* B3, long csB, long ldb, float* C, int M, int N, int K, int ldc) {
     g = X3Gemm{};
@@ -817,172 +870,93 @@ static int x3_launch_auto(const X3Gemm& g, hipStream_t s) {
     if (v == 1) return x3_launch_nt<2, 2, 2, 2, 3>(g, 6, s);
     return x3_launch_nt<2, 4, 2, 1, 3>(g, 6, s);
 }
-// y [N][OH][OW][Cout] (row stride ldy) = ConvTranspose2d(x [N][H][W][Cin] dense, w [Cin][KH][KW][Cout]) + bias, kernel == stride, pad 0
-int pdf_internal_x3_deconv_fwd(const float* x, const float* w, const float* bias, float* y, float* ws, int N, int H, int W, int Cin, int Cout,
-                               int KH, int KW, int stride, int OH, int OW, int ldy, hipStream_t s) {
-    const long M = (long)N * H * W, NT = (long)KH * KW * Cout, ld = x3_ld(Cin);
-    unsigned short* w3 = reinterpret_cast<unsigned short*>(ws);
-    unsigned short* x3 = reinterpret_cast<unsigned short*>(ws + ((3 * NT * ld + 1) / 2 + 3) / 4 * 4);
-    {
-        KTimer kt("x3_split_transpose_kernel", 0.0, 10.0 * NT * Cin, s);
-        hipLaunchKernelGGL(x3_split_transpose_kernel, dim3((unsigned)cdiv(NT, 64), (unsigned)cdiv(Cin, 64)), dim3(256), 0, s, w, NT, w3, Cin, (int)NT, ld, NT * ld, X3TrJobs{});
-    }
-    hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(M * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, x, (long)Cin, x3, ld, M * ld, M, Cin / 8);
-    PDF_LAUNCH_CHECK();
-    X3Gemm g;
-    x3_gemm_desc(g, x3, M * ld, ld, w3, NT * ld, ld, y, (int)M, (int)NT, Cin, ldy);
-    g.ps_cout = Cout; g.ps_kw = KW; g.ps_s = stride; g.QH = H; g.QW = W; g.OH = OH; g.OW = OW; g.bias = bias;
-    return x3_launch_auto(g, s);
-}
-// dx [N][H][W][Cin] (row stride lddx) = the input gradient of that layer from dy [N][OH][OW][Cout] (row stride lddy)
-int pdf_internal_x3_deconv_bwd_data(const float* dy, const float* w, float* dx, float* ws, int N, int H, int W, int Cin, int lddx, int Cout,
-                                    int KH, int KW, int stride, int OH, int OW, int lddy, hipStream_t s) {
-    const long M = (long)N * H * W, NT = (long)KH * KW * Cout, ld = x3_ld(NT);
-    unsigned short* w3 = reinterpret_cast<unsigned short*>(ws);
-    unsigned short* d3 = reinterpret_cast<unsigned short*>(ws + ((3 * Cin * ld + 1) / 2 + 3) / 4 * 4);
-    {
-        KTimer kt("x3_split_rows_kernel", 0.0, 10.0 * NT * Cin, s);
-        hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(NT * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, w, NT, w3, ld, Cin * ld, (long)Cin, (int)(NT / 8));
-    }
-    {
-        KTimer kt("x3_split_unshuffle_kernel", 0.0, 10.0 * M * NT, s);
-        hipLaunchKernelGGL(x3_split_unshuffle_kernel, dim3(grid_for(M * NT / 8, 256, 256 * 16)), dim3(256), 0, s, dy, lddy, d3, ld, M * ld, M, H, W, OH, OW, stride, Cout);
-    }
-    PDF_LAUNCH_CHECK();
-    X3Gemm g;
-    x3_gemm_desc(g, d3, M * ld, ld, w3, Cin * ld, ld, dx, (int)M, Cin, (int)NT, lddx);
-    return x3_launch_auto(g, s);
-}
-
-// dw [Cin][KH][KW][Cout] (+)= the weight gradient of that layer: sum over the input pixels m of x[m][ci] dy_unshuffled[m][(tap, co)] -- one x3gemm_tn launch,
-// no split of the reduction (p5: 2,048 rows against 2,048 output tiles), the accumulation into an existing gradient done by the epilogue
-int pdf_internal_x3_deconv_bwd_weight(const float* x, const float* dy, float* dw, float* ws, int N, int H, int W, int Cin, int Cout,
-                                      int KH, int KW, int stride, int OH, int OW, int lddy, int accumulate, hipStream_t s) {
-    const long M = (long)N * H * W, NT = (long)KH * KW * Cout, ldx3 = x3_ld(Cin), ldd = x3_ld(NT);
-    unsigned short* x3 = reinterpret_cast<unsigned short*>(ws);
-    unsigned short* d3 = reinterpret_cast<unsigned short*>(ws + ((3 * M * ldx3 + 1) / 2 + 3) / 4 * 4);
-    hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(M * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, x, (long)Cin, x3, ldx3, M * ldx3, M, Cin / 8);
-    {
-        KTimer kt("x3_split_unshuffle_kernel", 0.0, 10.0 * M * NT, s);
-        hipLaunchKernelGGL(x3_split_unshuffle_kernel, dim3(grid_for(M * NT / 8, 256, 256 * 16)), dim3(256), 0, s, dy, lddy, d3, ldd, M * ldd, M, H, W, OH, OW, stride, Cout);
-    }
-    PDF_LAUNCH_CHECK();
-    X3Gemm g = {};
-    g.A = x3; g.B = d3; g.C = dw;
-    g.csA = M * ldx3; g.csB = M * ldd; g.lda = (int)ldx3; g.ldb = (int)ldd;
-    g.M = Cin; g.N = (int)NT; g.K = (int)M; g.batch = 1; g.splits = 1; g.rows_per_split = (int)M; g.accum = accumulate;
-    return x3_launch_tn_deconv(g, s);
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// Transposed convolutions whose kernel is a multiple of the stride (the pyramid's p3: 512 -> 256, k = 4, s = 2, pad = 1; intaghand_encoder.py:602):
-//   forward        s x s parity classes of output pixels, each an implicit GEMM over its (k / s)^2 taps: rows = the class's pixels (qy, qx), A = x at
-//                  (qy + dy[t], qx + dx[t]) (zero outside the map), B = the class's taps of w gathered and transposed by the pre-pass, output scattered
-//                  to (qy s + py, qx s + px);
-//   backward-data  ONE implicit GEMM: rows = input pixels (iy, ix), A = dy at (iy s - pad + ky, ix s - pad + kx) over all k^2 taps, B = w as it lies.
-// Same x3gemm_nt kernel (template IM): the tap's pixel offset is applied per lane when the tap changes, its channels advance by the scalar offset.
-static bool x3_general_ok(int Cin, int Cout, int K, int stride, int pad) {
-    return K % stride == 0 && K * K <= 16 && K > stride && pad >= 0 && pad < K && Cin % 32 == 0 && Cout % 32 == 0;
-}
-static int x3_general_wgrad_splits(long M, int NI, long NJ) {      // ~2 blocks per CU, at least 64 K-steps per block
-    const long tiles = (long)cdiv(NI, 128) * cdiv(NJ, 128);
-    long sp = (512 + tiles - 1) / tiles;
-    if (sp > M / 2048) sp = M / 2048;
-    return (int)(sp < 1 ? 1 : sp);
-}
-static long x3_deconv_general_workspace(int N, int H, int W, int Cin, int Cout, int K, int stride, int pad, int backward) {
-    if (!x3_general_ok(Cin, Cout, K, stride, pad)) return 0;
-    const int OH = (H - 1) * stride - 2 * pad + K, OW = (W - 1) * stride - 2 * pad + K;
-    if (OH % stride != 0 || OW % stride != 0) return 0;
-    const long Min = (long)N * H * W, Mout = (long)N * OH * OW, T = (long)(K / stride) * (K / stride);
-    if (2.0 * Min * K * K * Cin * Cout < 3.0e10) return 0;
-    long ael, bel;
-    if (backward == 2) {                                     // P = x, Q = dy (+ zero row), slabs of the split reduction
-        if ((H & (H - 1)) || (W & (W - 1)) || Min % 32 != 0 || Cout % 128 != 0) return 0;
-        const long pel = Min * x3_ld(Cin), qel = (Mout + 1) * x3_ld(Cout);
-        if (3.0 * pel >= 2147483000.0 || 3.0 * qel >= 2147483000.0) return 0;
-        return ((3 * pel + 1) / 2 + 3) / 4 * 4 + ((3 * qel + 1) / 2 + 3) / 4 * 4 + (long)x3_general_wgrad_splits(Min, Cin, (long)K * K * Cout) * Cin * K * K * Cout + 64;
-    }
-    if (backward == 0) { ael = (Min + 1) * x3_ld(Cin); bel = (long)stride * stride * Cout * x3_ld(T * Cin); }
-    else { ael = (Mout + 1) * x3_ld(Cout); bel = (long)Cin * x3_ld((long)K * K * Cout); }
-    if (3.0 * ael >= 2147483000.0 || 3.0 * bel >= 2147483000.0) return 0;
-    return ((3 * bel + 1) / 2 + 3) / 4 * 4 + ((3 * ael + 1) / 2 + 3) / 4 * 4 + 64;
-}
-static int x3_zero_rows(unsigned short* a3, long rows, long ld, hipStream_t s) {      // the zero row behind each component plane
+static int x3_zero_rows(unsigned short* o3, const X3Operand& o, hipStream_t s) {      // the zero row behind each component plane
     for (int c = 0; c < 3; ++c)
-        if (hipMemsetAsync(a3 + c * (rows + 1) * ld + rows * ld, 0, (size_t)ld * 2, s) != hipSuccess) return PDF_E_BADARG;
+        if (hipMemsetAsync(o3 + c * o.cs + o.cs - o.ld, 0, (size_t)o.ld * 2, s) != hipSuccess) return PDF_E_BADARG;
     return 0;
 }
-int pdf_internal_x3_deconv_general_fwd(const float* x, const float* w, const float* bias, float* y, float* ws, int N, int H, int W, int Cin, int Cout,
-                                       int K, int stride, int pad, int OH, int OW, int ldy, hipStream_t s) {
-    const long Min = (long)N * H * W;
-    const int kk = K / stride, T = kk * kk, P = stride * stride;
-    const long ldA = x3_ld(Cin), ldB = x3_ld((long)T * Cin);
-    unsigned short* b3 = reinterpret_cast<unsigned short*>(ws);
-    unsigned short* a3 = reinterpret_cast<unsigned short*>(ws + ((3 * P * Cout * ldB + 1) / 2 + 3) / 4 * 4);
-    // taps of parity class (py, px), in the order both operands use
-    int tky[4][16], tkx[4][16];
-    X3TrJobs jobs = {};
-    if (P > 4 || P * T > 16) return PDF_E_BADARG;
-    for (int py = 0; py < stride; ++py)
-        for (int px = 0; px < stride; ++px) {
-            int n = 0;
-            for (int ky = 0; ky < K; ++ky) {
-                if (((py + pad - ky) % stride + stride) % stride != 0) continue;
-                for (int kx = 0; kx < K; ++kx) {
-                    if (((px + pad - kx) % stride + stride) % stride != 0) continue;
-                    const int pc = py * stride + px;
-                    tky[pc][n] = ky; tkx[pc][n] = kx;
-                    jobs.in_off[pc * T + n] = (long)(ky * K + kx) * Cout;
-                    jobs.out_off[pc * T + n] = (long)pc * Cout * ldB + (long)n * Cin;
-                    ++n;
-                }
-            }
-            if (n != T) return PDF_E_BADARG;
+static void x3_split_unshuffle(const float* dy, int lddy, unsigned short* o3, const X3DeconvPlan& p, hipStream_t s) {
+    const long M = (long)p.N * p.H * p.W, NT = (long)p.K * p.K * p.Cout;
+    KTimer kt("x3_split_unshuffle_kernel", 0.0, 10.0 * M * NT, s);
+    hipLaunchKernelGGL(x3_split_unshuffle_kernel, dim3(grid_for(M * NT / 8, 256, 256 * 16)), dim3(256), 0, s, dy, lddy, o3, p.a.ld, p.a.cs, M, p.H, p.W, p.OH, p.OW, p.stride, p.Cout);
+}
+static void x3_all_taps(X3Gemm& g, const X3DeconvPlan& p) {      // the gathered operand of the general backward passes: dy at (iy s - pad + ky, ix s - pad + kx), zero outside
+    g.QH = p.H; g.QW = p.W; g.AH = p.OH; g.AW = p.OW; g.sy = p.stride; g.sx = p.stride; g.T = p.K * p.K; g.Cc = p.Cout; g.zrow = p.a.cs - p.a.ld;
+    for (int ky = 0; ky < p.K; ++ky)
+        for (int kx = 0; kx < p.K; ++kx) { g.tdy[ky * p.K + kx] = ky - p.pad; g.tdx[ky * p.K + kx] = kx - p.pad; }
+}
+// y [N][OH][OW][Cout] (row stride ldy) = ConvTranspose2d(x [N][H][W][Cin] dense, w [Cin][K][K][Cout]) + bias
+int pdf_internal_x3_deconv_fwd(const X3DeconvPlan& p, const float* x, const float* w, const float* bias, float* y, float* ws, int ldy, hipStream_t s) {
+    const int N = p.N, H = p.H, W = p.W, Cin = p.Cin, Cout = p.Cout, K = p.K, stride = p.stride;
+    const long M = (long)N * H * W;
+    unsigned short* w3 = reinterpret_cast<unsigned short*>(ws + p.w.off);
+    unsigned short* x3 = reinterpret_cast<unsigned short*>(ws + p.a.off);
+    if (!p.general) {
+        const long NT = (long)K * K * Cout;
+        {
+            KTimer kt("x3_split_transpose_kernel", 0.0, 10.0 * NT * Cin, s);
+            hipLaunchKernelGGL(x3_split_transpose_kernel, dim3((unsigned)cdiv(NT, 64), (unsigned)cdiv(Cin, 64)), dim3(256), 0, s, w, NT, w3, Cin, (int)NT, p.w.ld, p.w.cs, X3TrJobs{});
         }
+        hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(M * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, x, (long)Cin, x3, p.a.ld, p.a.cs, M, Cin / 8);
+        PDF_LAUNCH_CHECK();
+        X3Gemm g;
+        x3_gemm_desc(g, x3, p.a.cs, p.a.ld, w3, p.w.cs, p.w.ld, y, (int)M, (int)NT, Cin, ldy);
+        g.ps_cout = Cout; g.ps_kw = K; g.ps_s = stride; g.QH = H; g.QW = W; g.OH = p.OH; g.OW = p.OW; g.bias = bias;
+        return x3_launch_auto(g, s);
+    }
+    const int T = (K / stride) * (K / stride), P = stride * stride;
+    if (P > 4 || P * T > 16) return PDF_E_BADARG;
+    // taps of every parity class (py, px), in the order both operands use
+    int tdy[4][16], tdx[4][16], wt[16];
+    X3TrJobs jobs = {};
+    for (int pc = 0; pc < P; ++pc) {
+        if (pdf_parity_taps(K, K, stride, p.pad, pc / stride, pc % stride, tdy[pc], tdx[pc], wt) != T) return PDF_E_BADARG;
+        for (int n = 0; n < T; ++n) {
+            jobs.in_off[pc * T + n] = (long)wt[n] * Cout;
+            jobs.out_off[pc * T + n] = (long)pc * Cout * p.w.ld + (long)n * Cin;
+        }
+    }
     {
         KTimer kt("x3_split_transpose_kernel", 0.0, 10.0 * K * K * Cout * Cin, s);
         hipLaunchKernelGGL(x3_split_transpose_kernel, dim3((unsigned)cdiv(Cout, 64), (unsigned)cdiv(Cin, 64), (unsigned)(P * T)), dim3(256), 0, s,
-                           w, (long)K * K * Cout, b3, Cin, Cout, ldB, (long)P * Cout * ldB, jobs);
+                           w, (long)K * K * Cout, w3, Cin, Cout, p.w.ld, p.w.cs, jobs);
     }
-    hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(Min * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, x, (long)Cin, a3, ldA, (Min + 1) * ldA, Min, Cin / 8);
-    if (int rc = x3_zero_rows(a3, Min, ldA, s)) return rc;
+    hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(M * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, x, (long)Cin, x3, p.a.ld, p.a.cs, M, Cin / 8);
+    if (int rc = x3_zero_rows(x3, p.a, s)) return rc;
     PDF_LAUNCH_CHECK();
-    for (int py = 0; py < stride; ++py)
-        for (int px = 0; px < stride; ++px) {
-            const int pc = py * stride + px, QH = (OH - py + stride - 1) / stride, QW = (OW - px + stride - 1) / stride;
-            X3Gemm g;
-            x3_gemm_desc(g, a3, (Min + 1) * ldA, ldA, b3 + (long)pc * Cout * ldB, (long)P * Cout * ldB, ldB, y, N * QH * QW, Cout, T * Cin, ldy);
-            g.ps_cout = Cout; g.ps_kw = 1; g.ps_s = stride; g.QH = QH; g.QW = QW; g.OH = OH; g.OW = OW; g.ooy = py; g.oox = px; g.bias = bias;
-            g.AH = H; g.AW = W; g.sy = 1; g.sx = 1; g.T = T; g.Cc = Cin; g.zrow = Min * ldA;
-            for (int n = 0; n < T; ++n) {                      // iy = qy + (py + pad - ky) / stride (exact division: the tap belongs to the class)
-                g.tdy[n] = (py + pad - tky[pc][n]) / stride; g.tdx[n] = (px + pad - tkx[pc][n]) / stride;
-            }
-            if (int rc = x3_launch_auto(g, s)) return rc;
-        }
+    for (int pc = 0; pc < P; ++pc) {
+        const int py = pc / stride, px = pc % stride, QH = (p.OH - py + stride - 1) / stride, QW = (p.OW - px + stride - 1) / stride;
+        X3Gemm g;
+        x3_gemm_desc(g, x3, p.a.cs, p.a.ld, w3 + (long)pc * Cout * p.w.ld, p.w.cs, p.w.ld, y, N * QH * QW, Cout, T * Cin, ldy);
+        g.ps_cout = Cout; g.ps_kw = 1; g.ps_s = stride; g.QH = QH; g.QW = QW; g.OH = p.OH; g.OW = p.OW; g.ooy = py; g.oox = px; g.bias = bias;
+        g.AH = H; g.AW = W; g.sy = 1; g.sx = 1; g.T = T; g.Cc = Cin; g.zrow = p.a.cs - p.a.ld;
+        for (int n = 0; n < T; ++n) { g.tdy[n] = tdy[pc][n]; g.tdx[n] = tdx[pc][n]; }      // iy = qy + tdy[n]
+        if (int rc = x3_launch_auto(g, s)) return rc;
+    }
     return 0;
 }
-int pdf_internal_x3_deconv_general_bwd_data(const float* dy, const float* w, float* dx, float* ws, int N, int H, int W, int Cin, int lddx, int Cout,
-                                            int K, int stride, int pad, int OH, int OW, int lddy, hipStream_t s) {
-    const long Mout = (long)N * OH * OW, M = (long)N * H * W, NT = (long)K * K * Cout;
-    const long ldA = x3_ld(Cout), ldB = x3_ld(NT);
-    unsigned short* b3 = reinterpret_cast<unsigned short*>(ws);
-    unsigned short* a3 = reinterpret_cast<unsigned short*>(ws + ((3 * Cin * ldB + 1) / 2 + 3) / 4 * 4);
+// dx [N][H][W][Cin] (row stride lddx) = the input gradient of that layer from dy [N][OH][OW][Cout] (row stride lddy)
+int pdf_internal_x3_deconv_bwd_data(const X3DeconvPlan& p, const float* dy, const float* w, float* dx, float* ws, int lddx, int lddy, hipStream_t s) {
+    const int Cin = p.Cin, Cout = p.Cout;
+    const long M = (long)p.N * p.H * p.W, Mout = (long)p.N * p.OH * p.OW, NT = (long)p.K * p.K * Cout;
+    unsigned short* w3 = reinterpret_cast<unsigned short*>(ws + p.w.off);
+    unsigned short* d3 = reinterpret_cast<unsigned short*>(ws + p.a.off);
     {
         KTimer kt("x3_split_rows_kernel", 0.0, 10.0 * NT * Cin, s);
-        hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(NT * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, w, NT, b3, ldB, Cin * ldB, (long)Cin, (int)(NT / 8));
+        hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(NT * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, w, NT, w3, p.w.ld, p.w.cs, (long)Cin, (int)(NT / 8));
     }
-    {
-        KTimer kt("x3_split_rows_kernel", 0.0, 10.0 * Mout * Cout, s);
-        hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(Mout * Cout / 8, 256, 256 * 16)), dim3(256), 0, s, dy, (long)lddy, a3, ldA, (Mout + 1) * ldA, Mout, Cout / 8);
-    }
-    if (int rc = x3_zero_rows(a3, Mout, ldA, s)) return rc;
-    PDF_LAUNCH_CHECK();
     X3Gemm g;
-    x3_gemm_desc(g, a3, (Mout + 1) * ldA, ldA, b3, Cin * ldB, ldB, dx, (int)M, Cin, (int)NT, lddx);
-    g.QH = H; g.QW = W; g.AH = OH; g.AW = OW; g.sy = stride; g.sx = stride; g.T = K * K; g.Cc = Cout; g.zrow = Mout * ldA;
-    for (int ky = 0; ky < K; ++ky)
-        for (int kx = 0; kx < K; ++kx) { g.tdy[ky * K + kx] = ky - pad; g.tdx[ky * K + kx] = kx - pad; }
+    x3_gemm_desc(g, d3, p.a.cs, p.a.ld, w3, p.w.cs, p.w.ld, dx, (int)M, Cin, (int)NT, lddx);
+    if (!p.general) x3_split_unshuffle(dy, lddy, d3, p, s);
+    else {
+        {
+            KTimer kt("x3_split_rows_kernel", 0.0, 10.0 * Mout * Cout, s);
+            hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(Mout * Cout / 8, 256, 256 * 16)), dim3(256), 0, s, dy, (long)lddy, d3, p.a.ld, p.a.cs, Mout, Cout / 8);
+        }
+        if (int rc = x3_zero_rows(d3, p.a, s)) return rc;
+        x3_all_taps(g, p);
+    }
+    PDF_LAUNCH_CHECK();
     return x3_launch_auto(g, s);
 }
 
@@ -995,35 +969,35 @@ __global__ __launch_bounds__(256) void x3_slab_reduce_kernel(const float* __rest
         reinterpret_cast<float4*>(dw)[i] = v;
     }
 }
-// dw [Cin][K][K][Cout] (+)= the weight gradient of the general form: sum over input pixels m of x[m][ci] dy[pixel(m, tap)][co] -- x3gemm_tn with the Q operand
-// gathered per tap (template IQ), the reduction split over the chip, the splits summed into dw
-int pdf_internal_x3_deconv_general_bwd_weight(const float* x, const float* dy, float* dw, float* ws, int N, int H, int W, int Cin, int Cout,
-                                              int K, int stride, int pad, int OH, int OW, int lddy, int accumulate, hipStream_t s) {
-    const long Min = (long)N * H * W, Mout = (long)N * OH * OW, NT = (long)K * K * Cout;
-    const long ldP = x3_ld(Cin), ldQ = x3_ld(Cout);
-    unsigned short* p3 = reinterpret_cast<unsigned short*>(ws);
-    float* wq = ws + ((3 * Min * ldP + 1) / 2 + 3) / 4 * 4;
-    unsigned short* q3 = reinterpret_cast<unsigned short*>(wq);
-    float* slab = wq + ((3 * (Mout + 1) * ldQ + 1) / 2 + 3) / 4 * 4;
-    hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(Min * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, x, (long)Cin, p3, ldP, Min * ldP, Min, Cin / 8);
+// dw [Cin][K][K][Cout] (+)= the weight gradient of that layer: sum over the input pixels m of x[m][ci] dy[pixel(m, tap)][co] -- one x3gemm_tn launch.
+// kernel == stride: dy unshuffled to [m][(tap, co)], no split of the reduction (p5: 2,048 rows against 2,048 output tiles), the accumulation into an
+// existing gradient done by the epilogue; general form: the Q operand gathered per tap (template IQ), the reduction split over the chip, the splits summed into dw
+int pdf_internal_x3_deconv_bwd_weight(const X3DeconvPlan& p, const float* x, const float* dy, float* dw, float* ws, int lddy, int accumulate, hipStream_t s) {
+    const int Cin = p.Cin, Cout = p.Cout;
+    const long M = (long)p.N * p.H * p.W, Mout = (long)p.N * p.OH * p.OW, NT = (long)p.K * p.K * Cout;
+    unsigned short* x3 = reinterpret_cast<unsigned short*>(ws + p.w.off);
+    unsigned short* d3 = reinterpret_cast<unsigned short*>(ws + p.a.off);
+    hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(M * Cin / 8, 256, 256 * 16)), dim3(256), 0, s, x, (long)Cin, x3, p.w.ld, p.w.cs, M, Cin / 8);
+    X3Gemm g = {};
+    g.A = x3; g.B = d3; g.C = dw;
+    g.csA = p.w.cs; g.csB = p.a.cs; g.lda = (int)p.w.ld; g.ldb = (int)p.a.ld;
+    g.M = Cin; g.N = (int)NT; g.K = (int)M; g.batch = 1; g.splits = 1; g.rows_per_split = (int)M; g.accum = accumulate;
+    if (!p.general) {
+        x3_split_unshuffle(dy, lddy, d3, p, s);
+        PDF_LAUNCH_CHECK();
+        return x3_launch_tn_deconv(g, s);
+    }
     {
         KTimer kt("x3_split_rows_kernel", 0.0, 10.0 * Mout * Cout, s);
-        hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(Mout * Cout / 8, 256, 256 * 16)), dim3(256), 0, s, dy, (long)lddy, q3, ldQ, (Mout + 1) * ldQ, Mout, Cout / 8);
+        hipLaunchKernelGGL(x3_split_rows_kernel, dim3(grid_for(Mout * Cout / 8, 256, 256 * 16)), dim3(256), 0, s, dy, (long)lddy, d3, p.a.ld, p.a.cs, Mout, Cout / 8);
     }
-    if (int rc = x3_zero_rows(q3, Mout, ldQ, s)) return rc;
+    if (int rc = x3_zero_rows(d3, p.a, s)) return rc;
     PDF_LAUNCH_CHECK();
-    const int splits = x3_general_wgrad_splits(Min, Cin, NT);
-    X3Gemm g = {};
-    g.A = p3; g.B = q3; g.C = splits > 1 ? slab : dw;
-    g.csA = Min * ldP; g.csB = (Mout + 1) * ldQ; g.lda = (int)ldP; g.ldb = (int)ldQ;
-    g.M = Cin; g.N = (int)NT; g.K = (int)Min; g.batch = 1;
-    g.rows_per_split = cdiv(cdiv(Min, splits), 32) * 32; g.splits = cdiv(Min, g.rows_per_split);
-    g.accum = (g.splits == 1) ? accumulate : 0;
-    g.QH = H; g.QW = W; g.AH = OH; g.AW = OW; g.sy = stride; g.sx = stride; g.T = K * K; g.Cc = Cout; g.zrow = Mout * ldQ;
-    g.lw = __builtin_ctz(W); g.lhw = __builtin_ctz(H * W);
-    for (int ky = 0; ky < K; ++ky)
-        for (int kx = 0; kx < K; ++kx) { g.tdy[ky * K + kx] = ky - pad; g.tdx[ky * K + kx] = kx - pad; }
-    if (g.splits == 1) g.C = dw;
+    float* slab = ws + p.slab.off;
+    g.rows_per_split = cdiv(cdiv(M, p.splits), 32) * 32; g.splits = cdiv(M, g.rows_per_split);
+    if (g.splits > 1) { g.C = slab; g.accum = 0; }
+    x3_all_taps(g, p);
+    g.lw = __builtin_ctz(p.W); g.lhw = __builtin_ctz(p.H * p.W);
     if (int rc = x3_launch_tn_deconv(g, s)) return rc;
     if (g.splits > 1) {
         KTimer kt("x3_slab_reduce_kernel", 0.0, 4.0 * (g.splits + 1) * Cin * NT, s);
@@ -1031,4 +1005,28 @@ int pdf_internal_x3_deconv_general_bwd_weight(const float* x, const float* dy, f
         PDF_LAUNCH_CHECK();
     }
     return 0;
+}
+
+// The plan of a launch as numbers (header: pdf_debug_workspace_plan), so that a layout can be checked without a device
+PDF_API int pdf_debug_workspace_plan(int kind, int pass, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, long* out, int cap) {
+    long v[8 + 2 * 4] = {0, 0, 0, 0, 0, -1, -1, 0};
+    WsRegion r[4];
+    int n = 0;
+    if (kind == 0 && pass == 2) {
+        const WinoWgradPlan p = wino_wgrad_plan(N, H, W, Cin, Cout, KH, KW, stride, pad);
+        v[0] = p.ok; v[1] = p.total; v[2] = p.ok ? 4 : 0; v[3] = p.x3; v[4] = p.splits; v[6] = p.shared_v_x3;
+        if (p.ok) { r[0] = p.V; r[1] = p.Yh; r[2] = p.slab; r[3] = p.colsum; n = 4; }
+    } else if (kind == 0) {
+        const WinoPlan p = wino_plan(N, H, W, pass ? Cout : Cin, pass ? Cin : Cout, KH, KW, stride, pad, pass);
+        v[0] = p.ok; v[1] = p.total; v[2] = p.m; v[3] = p.x3; v[5] = p.v_offset; v[6] = p.shared_v_x3;
+        if (p.ok) { r[0] = p.U; r[1] = p.V; r[2] = p.M; n = 3; }
+    } else {
+        const X3DeconvPlan p = pdf_debug_gemm_precision() ? X3DeconvPlan{} : x3_deconv_plan(N, H, W, Cin, Cout, KH, KW, stride, pad, pass);
+        v[0] = p.ok; v[1] = p.total; v[2] = p.general; v[3] = p.ok; v[4] = p.splits;
+        if (p.ok) { r[0] = {p.w.off, p.w.len}; r[1] = {p.a.off, p.a.len}; r[2] = p.slab; n = p.slab.len > 0 ? 3 : 2; }
+    }
+    v[7] = n;
+    for (int i = 0; i < n; ++i) { v[8 + 2 * i] = r[i].off; v[9 + 2 * i] = r[i].len; }
+    for (int i = 0; i < 8 + 2 * n && i < cap; ++i) out[i] = v[i];
+    return 8 + 2 * n;
 }

@@ -226,26 +226,32 @@ def _O(**kw):
 # workspace is a fresh torch.empty per call (GB-scale for `feat`: the caching allocator keeps a few such blocks per stream).
 WINOGRAD = _os.environ.get("PDFNET_WINOGRAD", "1") != "0"
 WINOGRAD_INFERENCE = _os.environ.get("PDFNET_WINOGRAD_INFERENCE", "0") != "0"     # also for forwards without autograd (eval / no_grad)
-_wino_cache = {}
+_ws_sizes = {}           # (size query, its arguments) -> its result: workspace sizes and offsets depend on the shape and the x3 mode only
+
+
+def _ws_query(fn, *args):
+    """The library's answer to a workspace size / offset query, asked once per shape (set_x3 drops the answers)."""
+    n = _ws_sizes.get((fn, args))
+    if n is None:
+        n = _ws_sizes[(fn, args)] = getattr(_L(), fn)(*args)
+    return n
+
+
+def _ws_alloc(n, dev):
+    return (torch.empty(n, dtype=torch.float32, device=dev), n) if n > 0 else (None, None)
 
 
 def _wino_ws(N, H, W, Cin, Cout, KH, KW, stride, pad, backward, dev):
-    """-> (workspace tensor, floats) for the Winograd path of this convolution's forward (backward = 0) or backward-data pass, or (None, None)."""
+    """-> (workspace tensor, floats) for the Winograd path of this convolution's forward (backward = 0), backward-data (1) or
+    weight-gradient (2) pass, or (None, None)."""
     if not WINOGRAD or _GEMM_BF16 or KH != 3 or KW != 3 or stride != 1 or pad != 1 or Cin < 64 or Cout < 64:
         return None, None
-    key = (N, H, W, Cin, Cout, backward)
-    n = _wino_cache.get(key)
-    if n is None:
-        n = _wino_cache[key] = _L().pdf_conv2d_winograd_workspace_floats(N, H, W, Cin, Cout, KH, KW, stride, pad, backward)
-    if n <= 0:
-        return None, None
-    return torch.empty(n, dtype=torch.float32, device=dev), n
+    return _ws_alloc(_ws_query("pdf_conv2d_winograd_workspace_floats", N, H, W, Cin, Cout, KH, KW, stride, pad, backward), dev)
 
 
 # x3 arithmetic for the pyramid's kernel == stride transposed convolutions (csrc/gemm_x3.hip: fp32 products as six bf16 MFMAs on 3-way split
 # operands, fp32-exact to ~2^-24): the library asks for a workspace for the split operands; 0 floats = the layer does not qualify.
 X3_DECONV = _os.environ.get("PDFNET_X3_DECONV", "1") != "0"
-_x3d_cache = {}
 
 
 def set_x3(mode):
@@ -253,35 +259,22 @@ def set_x3(mode):
     transposed convolutions, bit 2 the fused mesh decoder's linear products; None = the environment's choice).  Drops the cached workspace sizes, which
     depend on it; recorded tapes (taped.py) compare the mode on every call and are dropped there."""
     _L().pdf_set_x3_mode(-1 if mode is None else int(mode))
-    _wino_cache.clear()
-    _wino_voff.clear()
-    _x3d_cache.clear()
+    _ws_sizes.clear()
 
 
 def _x3_deconv_ws(N, H, W, Cin, Cout, KH, KW, stride, pad, backward, dev):
     if not X3_DECONV or _GEMM_BF16 or KH != KW or stride < 2:
         return None, None
-    key = (N, H, W, Cin, Cout, KH, stride, pad, backward)
-    n = _x3d_cache.get(key)
-    if n is None:
-        n = _x3d_cache[key] = _L().pdf_deconv2d_x3_workspace_floats(N, H, W, Cin, Cout, KH, KW, stride, pad, backward)
-    if n <= 0:
-        return None, None
-    return torch.empty(n, dtype=torch.float32, device=dev), n
+    return _ws_alloc(_ws_query("pdf_deconv2d_x3_workspace_floats", N, H, W, Cin, Cout, KH, KW, stride, pad, backward), dev)
 
 
 WINOGRAD_KEEP_V = _os.environ.get("PDFNET_WINOGRAD_KEEP_V", "1") != "0"
-_wino_voff = {}
 
 
 def _wino_v_offset(N, H, W, Cin, Cout, KH, KW, stride, pad):
     """Float offset of the transformed input V inside this convolution's forward Winograd workspace, or -1 (no F(4x4) forward, or the
     weight gradient does not take the Winograd path)."""
-    key = (N, H, W, Cin, Cout, KH, KW, stride, pad)
-    off = _wino_voff.get(key)
-    if off is None:
-        off = _wino_voff[key] = _L().pdf_conv2d_winograd_v_offset(N, H, W, Cin, Cout, KH, KW, stride, pad)
-    return off
+    return _ws_query("pdf_conv2d_winograd_v_offset", N, H, W, Cin, Cout, KH, KW, stride, pad)
 
 
 WINOGRAD_SHARE = _os.environ.get("PDFNET_WINOGRAD_SHARE", "1") != "0"

@@ -1,7 +1,7 @@
 """Which GEMM-family kernel every parity case runs, and that kernel against float64.
 
 The host picks between some 25 kernels of csrc/gemm.hip, gemm_x3.hip and winograd.hip by shape thresholds (launch_igemm, launch_wgemm,
-pdf_internal_wino_tile / wino_x3, the streaming and stem special cases).  A test that only chooses a shape "for" a kernel goes on
+wino_plan / wino_wgrad_plan of csrc/winograd.hip, the streaming and stem special cases).  A test that only chooses a shape "for" a kernel goes on
 passing when a threshold or a default moves the shape to another kernel.  Every row here therefore states the kernel records
 (tests/util.py kernels_run: the names the sources give to KTimer) it expects of its forward and of its backward, in launch order and
 in full -- so no other GEMM-family kernel can stand in -- and, for 3x3 stride-1 convolutions, which of the three launches take the
@@ -231,7 +231,7 @@ WINO_ROWS = [
     row("wino-f4-c144-c80", 'conv', (2, 144, 64, 64, 80, 3, 1, 1, 0, False), [IG64_16], [IG64_16_KN, WG_DMA], wino=(True, False, True)),
     # H % 4 != 0: F(2x2), T = 4 x 17 x 17 = 1156 tiles (not a multiple of 128; 16 T >= 16384); no Winograd weight gradient (F(4x4) only)
     row("wino-f2-fallback", 'conv', (4, 128, 34, 34, 64, 3, 1, 1, 0, False), [IG64_32], [IG64_32_KN, SKF, WG64, RS], wino=(True, False, False)),
-    # forward and backward-data Winograd, weight gradient direct: T = 3 x 13 x 13 = 507 is odd (pdf_internal_wino_wgrad_eligible: T % 16)
+    # forward and backward-data Winograd, weight gradient direct: T = 3 x 13 x 13 = 507 is odd (wino_wgrad_plan: T % 16)
     row("wino-f4-odd-t", 'conv', (3, 128, 52, 52, 128, 3, 1, 1, 0, False), [IG64_32], [IG64_32, WG64, RS], wino=(True, True, False)),
 ]
 
@@ -357,7 +357,7 @@ def test_x3_winograd_products_are_no_worse_than_the_native_ones(F, monkeypatch):
 @pytest.mark.parametrize("keep_v", [True, False])
 def test_x3_forward_whose_weight_gradient_is_native(F, monkeypatch, keep_v):
     """Cin = 256, T = 2048, Cout = 80 (% 32 != 0): the forward's V is x3, the weight gradient's products are native -- the cached V is in the
-    other format and pdf_internal_conv3x3_winograd_wgrad must transform the input again, whether the forward's workspace was kept
+    other format -- the plan records both -- and the weight gradient must transform the input again, whether the forward's workspace was kept
     (F.WINOGRAD_KEEP_V) or not.  (The backward-data's reduction runs over 80 < 128 channels: direct.)"""
     cfg = (8, 256, 64, 64, 80, 3, 1, 1, 0, False)
     case, bars = conv_case(cfg), conv_bars(cfg)
