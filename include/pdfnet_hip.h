@@ -675,6 +675,55 @@ int pdf_mano_fit(const float* target, const float* valid, const float* weight, c
                  int B, int left_side, int iters, float prior_pose, float prior_shape,
                  float* params, float* verts, float* joints, float* cost, int* info, float* lambda, float* A, float* g,
                  float* workspace, void* stream);
+/* Per-vertex targets of a MANO fit against the sensor cloud (csrc/icp.hip).  Row b is ONE hand: its mesh, its cloud.  Forward only.
+ * verts [B,n,3] f32 camera-space metres; faces [Fc,3] int64, that hand's faces oriented outwards (an index outside [0, n) is clamped); cloud
+ * [B,P,3] f32; valid [B] f32 or NULL; anchor [B,n,3] f32 or NULL; anchor_weight alpha >= 0 and finite, counted as 0 when anchor is NULL; trim.
+ * The association is that of pdf_mesh_icp with iters = 0, made by the same device code: a point with Z <= 0 is ignored; only the triangles
+ * that face the camera at the origin are candidates; q by the seven regions in the same order; the lowest face index wins a tie; p is an
+ * inlier when |p - q| < trim, strictly.  With q = w_a a + w_b b + w_c c (pdf_cloud_mesh_loss's weights) and d = p - q (fp32), vertex v collects
+ *   W_v = sum w_k  and  S_v = sum w_k d  over the (inlier, corner k) pairs that name v: d is the fp32 difference, the products and the sums
+ *   are carried in double, in ascending point order.  For any mesh M, sum_i |sum_k w_ik M_k - p_i|^2 <= sum_v W_v |M_v - (v + S_v / W_v)|^2 + const (Jensen),
+ *   with equality at M = verts: the weighted per-vertex energy that pdf_mano_fit minimises majorises the point-to-surface energy of this
+ *   association.  The anchor adds alpha |M_v - a_v|^2 per vertex and merges into the same form:
+ *   weight [B,n]   f32: fp32(W_v + alpha)
+ *   target [B,n,3] f32: fp32((W_v v + S_v + alpha a_v) / (W_v + alpha)), in double; where W_v = 0 exactly a_v when alpha > 0 and else v itself
+ *                  (weight 0), so a vertex that no inlier names is held by the anchor alone or not at all
+ *   rms [B] f32 and inliers [B] int32: as pdf_mesh_icp's
+ *   tri [B,P] int32, bary [B,P,3] f32, closest [B,P,3] f32, each or NULL: as pdf_cloud_mesh_loss's
+ * A row with valid = 0 or without a point that is not ignored still receives the anchor: W = 0, rms = 0, inliers = 0, tri = -1, bary = closest
+ * = 0, weight = alpha, target = a (target = v when alpha = 0).
+ * 1 <= n <= 1024, 1 <= Fc <= 2048, 1 <= P <= 1024, trim > 0 and finite, alpha >= 0 and finite, verts, faces, cloud, target, weight, rms and
+ * inliers not NULL, else PDF_E_BADARG with nothing launched; B <= 0 returns 0.  One launch, one workgroup per row, no atomics, no scratch
+ * memory: two runs are bit-identical and a row's result does not depend on the other rows of the batch. */
+int pdf_mano_cloud_targets(const float* verts, const long long* faces, const float* cloud, const float* valid, const float* anchor,
+                           float anchor_weight, int B, int n, int Fc, int P, float trim, float* target, float* weight, float* rms,
+                           int* inliers, int* tri, float* closest, float* bary, void* stream);
+/* MANO fit against the sensor cloud (csrc/manofit.hip): alternates pdf_mano_cloud_targets and pdf_mano_fit.  Row b is one hand.  Forward only;
+ * everything is enqueued on `stream` and nothing synchronises.
+ * cloud [B,P,3], faces [Fc,3] (of the 778-vertex MANO mesh), valid [B] or NULL, anchor [B,778,3] or NULL, anchor_weight, trim: as
+ * pdf_mano_cloud_targets takes them; init [B,61] f32, required; prior_pose, prior_shape, v_template ... weights, left_side: as pdf_mano_fit's.
+ *   params_0 = init, verts_0 = M(init): a launch of pdf_mano_fit's kernel with iters = 0.
+ *   for o = 0 .. outer - 1:  the targets at verts_o -> rms[o], inliers[o];  then `inner` Levenberg-Marquardt trial steps of pdf_mano_fit from
+ *       params_o against those targets and weights -> params_{o+1}, verts_{o+1}, cost[o], info[o].  Each outer iteration is a fresh
+ *       pdf_mano_fit: lambda RESTARTS at 1e-3 (the surrogate changes with the association, so the damping of the last one says little).
+ *   one more targets launch at verts_outer -> rms[outer], inliers[outer].
+ * An accepted step lowers the surrogate, which majorises the fixed-association energy: with the anchor and the priors counted in, that energy
+ * does not rise within an outer iteration.
+ * Outputs   params [B,61], verts [B,778,3] = M(params), joints [B,21,3]; rms [outer+1,B] f32, inliers [outer+1,B] int32; cost [outer,B,2] f32
+ *           and info [outer,B,2] int32 (pdf_mano_fit's, of each outer iteration; not touched when outer = 0).
+ * A row with valid = 0 keeps params = init and verts = M(init); its rms, inliers, cost and info are 0.
+ * workspace: pdf_mano_fit_cloud_workspace_floats(B, outer) floats of device memory, required: the targets, the weights, the second set of
+ * parameters (they alternate with `params`), the damping and the start launch's cost and counts.  It does not grow with `outer`.
+ * 0 <= outer <= 64, 1 <= inner <= 1000, 1 <= Fc <= 2048, 1 <= P <= 1024, trim > 0 and finite, anchor_weight and the priors >= 0 and finite,
+ * every pointer not called optional above not NULL, else PDF_E_BADARG with nothing launched; B <= 0 returns 0.  2 outer + 2 launches and one
+ * fill; two runs are bit-identical and a row's result does not depend on the other rows of the batch. */
+long pdf_mano_fit_cloud_workspace_floats(int B, int outer);
+int pdf_mano_fit_cloud(const float* cloud, const long long* faces, const float* valid, const float* init, const float* anchor,
+                       float anchor_weight, float trim, int outer, int inner, float prior_pose, float prior_shape,
+                       const float* v_template, const float* shapedirs, const float* posedirs, const float* J_reg, const float* weights,
+                       int B, int Fc, int P, int left_side,
+                       float* params, float* verts, float* joints, float* rms, int* inliers, float* cost, int* info,
+                       float* workspace, void* stream);
 
 
 /* ---- explicit per-call options (round 4) ------------------------------------------------------------------------------

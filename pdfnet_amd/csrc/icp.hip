@@ -256,3 +256,94 @@ PDF_API int pdf_cloud_mesh_loss(const float* verts, const long long* faces, cons
     PDF_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- per-vertex targets of a MANO fit against the cloud (contract: pdf_mano_cloud_targets in pdfnet_hip.h) ---------------------------------
+// cloud_mesh_loss_kernel's association once more -- icp_facing and icp_walk<true>, shared -- for ONE hand per row (faces [Fc][3], no hand
+// index).  An inlier's residual d = p - q goes to the three corners of its triangle with the weights w_k of q = wa a + wb b + wc c: vertex v
+// collects W_v = sum w_k and S_v = sum w_k d (geo_corner_gather_w: in double, ascending point order, no atomics), and the weighted per-vertex
+// energy sum_v W_v |M_v - (v + S_v / W_v)|^2 majorises the point-to-surface energy of the fixed association, with equality at M = verts.  The
+// anchor adds anchor_weight |M_v - a_v|^2 per vertex; both merge into one target and one weight, which is what mano_fit_kernel takes.
+__global__ __launch_bounds__(ICP_T) void mano_cloud_targets_kernel(const float* __restrict__ verts, const long long* __restrict__ faces,
+                                                                   const float* __restrict__ cloud, const float* __restrict__ valid,
+                                                                   const float* __restrict__ anchor, float alpha, int n, int Fc, int P, float trim,
+                                                                   float* __restrict__ target, float* __restrict__ weight, float* __restrict__ rms,
+                                                                   int* __restrict__ inliers, int* __restrict__ tri, float* __restrict__ closest,
+                                                                   float* __restrict__ bary) {
+    __shared__ IcpShared s;
+    const int t = threadIdx.x;
+    const long row = blockIdx.x;
+    const float* pp = cloud + (row * P + min(t, P - 1)) * 3;
+    const float* vp = verts + (row * n + min(t, n - 1)) * 3;
+    const float* ap = anchor != nullptr ? anchor + (row * n + min(t, n - 1)) * 3 : nullptr;
+    if (ap == nullptr) alpha = 0.f;
+    const bool live = t < P && pp[2] > 0.f;
+    const bool row_ok = valid == nullptr || valid[row] != 0.f;
+    if (!__syncthreads_or(live && row_ok)) {                   // block-uniform: nothing to compare the hand with; the anchor alone
+        if (t == 0) { rms[row] = 0.f; inliers[row] = 0; }
+        if (t < n) {
+            const float* src = alpha > 0.f ? ap : vp;
+            float* o = target + (row * n + t) * 3;
+            o[0] = src[0]; o[1] = src[1]; o[2] = src[2];
+            weight[row * n + t] = alpha;
+        }
+        if (t < P) {
+            if (closest != nullptr) { float* c = closest + (row * P + t) * 3; c[0] = c[1] = c[2] = 0.f; }
+            if (bary != nullptr) { float* w = bary + (row * P + t) * 3; w[0] = w[1] = w[2] = 0.f; }
+            if (tri != nullptr) tri[row * P + t] = -1;
+        }
+        return;
+    }
+    if (t < n) { s.vx[t] = vp[0]; s.vy[t] = vp[1]; s.vz[t] = vp[2]; }
+    geo_stage_faces(faces, Fc, n, s.tri);
+    __syncthreads();
+
+    const int count = icp_facing(s, Fc);                       // (ends in a barrier)
+    const float px = pp[0], py = pp[1], pz = pp[2];
+    float best = 3.0e38f, qx = 0.f, qy = 0.f, qz = 0.f, wa = 0.f, wb = 0.f, wc = 0.f;
+    int face = -1;
+    if (__ballot(live) != 0ULL) icp_walk<true>(s, count, px, py, pz, best, qx, qy, qz, face, wa, wb, wc);      // wave-uniform
+    const bool hit = live && face >= 0, in = hit && sqrtf(best) < trim;
+    double a[2] = {in ? 1.0 : 0.0, in ? (double)best : 0.0};
+    icp_block_sum<2>(a, s.red, s.sum);                         // (its barriers: every lane has left the walk, the corner list is dead)
+    if (t == 0) {
+        rms[row] = s.sum[0] > 0.0 ? (float)sqrt(s.sum[1] / s.sum[0]) : 0.f;
+        inliers[row] = (int)s.sum[0];
+    }
+    if (t < P) {
+        if (closest != nullptr) { float* c = closest + (row * P + t) * 3; c[0] = hit ? qx : 0.f; c[1] = hit ? qy : 0.f; c[2] = hit ? qz : 0.f; }
+        if (bary != nullptr) { float* w = bary + (row * P + t) * 3; w[0] = hit ? wa : 0.f; w[1] = hit ? wb : 0.f; w[2] = hit ? wc : 0.f; }
+        if (tri != nullptr) tri[row * P + t] = hit ? face : -1;
+    }
+    const double4 ws = geo_corner_gather_w(s, wa, wb, wc, in ? px - qx : 0.f, in ? py - qy : 0.f, in ? pz - qz : 0.f, in ? face : -1, P, n);
+    if (t < n) {
+        const double W = ws.w, den = W + (double)alpha;
+        const float vx = s.vx[t], vy = s.vy[t], vz = s.vz[t];
+        float* o = target + (row * n + t) * 3;
+        if (W == 0.0) {                                         // no inlier names the vertex: the anchor, or the vertex itself
+            const float* src = alpha > 0.f ? ap : vp;
+            o[0] = src[0]; o[1] = src[1]; o[2] = src[2];
+        } else {
+            const double ax = alpha > 0.f ? (double)alpha * ap[0] : 0.0, ay = alpha > 0.f ? (double)alpha * ap[1] : 0.0,
+                         az = alpha > 0.f ? (double)alpha * ap[2] : 0.0;
+            o[0] = (float)((W * vx + ws.x + ax) / den);
+            o[1] = (float)((W * vy + ws.y + ay) / den);
+            o[2] = (float)((W * vz + ws.z + az) / den);
+        }
+        weight[row * n + t] = (float)den;
+    }
+}
+
+PDF_API int pdf_mano_cloud_targets(const float* verts, const long long* faces, const float* cloud, const float* valid, const float* anchor,
+                                   float anchor_weight, int B, int n, int Fc, int P, float trim, float* target, float* weight, float* rms,
+                                   int* inliers, int* tri, float* closest, float* bary, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (B <= 0) return 0;
+    if (n < 1 || n > HAND_MAXN || Fc < 1 || Fc > HAND_MAXF || P < 1 || P > HAND_MAXP || !(trim > 0.f) || !(trim <= 3.0e38f) ||
+        !(anchor_weight >= 0.f) || !(anchor_weight <= 3.0e38f) || verts == nullptr || faces == nullptr || cloud == nullptr || target == nullptr ||
+        weight == nullptr || rms == nullptr || inliers == nullptr)
+        return PDF_E_BADARG;
+    hipLaunchKernelGGL(mano_cloud_targets_kernel, dim3(B), dim3(ICP_T), 0, s, verts, faces, cloud, valid, anchor, anchor_weight, n, Fc, P, trim,
+                       target, weight, rms, inliers, tri, closest, bary);
+    PDF_LAUNCH_CHECK();
+    return 0;
+}

@@ -514,3 +514,55 @@ PDF_API int pdf_mano_fit(const float* target, const float* valid, const float* w
     PDF_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- MANO fit against the sensor cloud (contract: pdf_mano_fit_cloud in pdfnet_hip.h) -----------------------------------------------------
+// The loop is host code: mano_cloud_targets_kernel (icp.hip) turns the association at the current mesh into per-vertex targets and weights,
+// mano_fit_kernel -- launched as pdf_mano_fit launches it -- takes `inner` steps against them.  The parameters alternate between `params` and
+// the workspace, started on the side that makes the last launch write `params`; every per-iteration output is a contiguous slice.
+namespace {
+constexpr long FC_TARGET = NR, FC_WEIGHT = NV, FC_PARAMS = NP, FC_SMALL = 5;      // per row: lambda, the start launch's cost [2] and info [2]
+}
+
+PDF_API long pdf_mano_fit_cloud_workspace_floats(int B, int outer) {
+    (void)outer;
+    return B > 0 ? (long)B * (FC_TARGET + FC_WEIGHT + FC_PARAMS + FC_SMALL) : 0;
+}
+
+PDF_API int pdf_mano_fit_cloud(const float* cloud, const long long* faces, const float* valid, const float* init, const float* anchor,
+                               float anchor_weight, float trim, int outer, int inner, float prior_pose, float prior_shape,
+                               const float* v_template, const float* shapedirs, const float* posedirs, const float* J_reg, const float* weights,
+                               int B, int Fc, int P, int left_side,
+                               float* params, float* verts, float* joints, float* rms, int* inliers, float* cost, int* info,
+                               float* workspace, void* stream) {
+    if (B <= 0) return 0;
+    if (cloud == nullptr || faces == nullptr || init == nullptr || v_template == nullptr || shapedirs == nullptr || posedirs == nullptr ||
+        J_reg == nullptr || weights == nullptr || params == nullptr || verts == nullptr || joints == nullptr || rms == nullptr ||
+        inliers == nullptr || workspace == nullptr || (outer > 0 && (cost == nullptr || info == nullptr)))
+        return PDF_E_BADARG;
+    if (outer < 0 || outer > 64 || inner < 1 || inner > 1000 || Fc < 1 || Fc > 2048 || P < 1 || P > 1024 || !(trim > 0.f) || !(trim <= 3.0e38f) ||
+        !(anchor_weight >= 0.f && anchor_weight <= 3.0e38f) || !(prior_pose >= 0.f && prior_pose <= 3.0e38f) ||
+        !(prior_shape >= 0.f && prior_shape <= 3.0e38f))
+        return PDF_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    float* target = workspace;
+    float* weight = target + (long)B * FC_TARGET;
+    float* other = weight + (long)B * FC_WEIGHT;
+    float* lambda = other + (long)B * FC_PARAMS;
+    float* cost0 = lambda + B;
+    int* info0 = reinterpret_cast<int*>(cost0 + 2L * B);
+    float* pp[2] = {params, other};
+    int cur = outer & 1;                                        // after `outer` swaps the parameters are in `params`
+    { hipError_t e = hipMemsetAsync(target, 0, sizeof(float) * (size_t)B * FC_TARGET, s); if (e != hipSuccess) return (int)e; }
+    int rc = pdf_mano_fit(target, valid, nullptr, init, v_template, shapedirs, posedirs, J_reg, weights, B, left_side, 0, prior_pose, prior_shape,
+                          pp[cur], verts, joints, cost0, info0, lambda, nullptr, nullptr, nullptr, stream);
+    for (int o = 0; o <= outer && rc == 0; ++o) {
+        rc = pdf_mano_cloud_targets(verts, faces, cloud, valid, anchor, anchor_weight, B, NV, Fc, P, trim, target, weight, rms + (long)o * B,
+                                    inliers + (long)o * B, nullptr, nullptr, nullptr, stream);
+        if (rc != 0 || o == outer) break;
+        rc = pdf_mano_fit(target, valid, weight, pp[cur], v_template, shapedirs, posedirs, J_reg, weights, B, left_side, inner, prior_pose,
+                          prior_shape, pp[cur ^ 1], verts, joints, cost + (long)o * B * 2, info + (long)o * B * 2, lambda, nullptr, nullptr,
+                          nullptr, stream);
+        cur ^= 1;
+    }
+    return rc;
+}

@@ -201,3 +201,29 @@ __device__ __forceinline__ double3 geo_corner_gather(IcpShared& s, float wa, flo
     }
     return make_double3(sx, sy, sz);
 }
+
+// geo_corner_gather with a fourth sum and exact products: .x .y .z = the sum of w_k g with every product taken in double (exact: two fp32
+// factors), added in double in ascending record order, and .w = the sum of the weights w_k themselves over the records that name vertex t.
+// A query with face = -1 adds to neither.
+__device__ __forceinline__ double4 geo_corner_gather_w(IcpShared& s, float wa, float wb, float wc, float gx, float gy, float gz, int face,
+                                                       int records, int n) {
+    const int t = threadIdx.x;
+    if (t < records) {
+        ushort4 f = make_ushort4(0xffff, 0xffff, 0xffff, 0);
+        if (face >= 0) f = s.tri[face];                        // face < Fc: it came out of the list
+        s.ca[t] = make_float4(wa, wb, wc, __int_as_float((int)f.x | ((int)f.y << 16)));
+        s.cb[t] = make_float4(gx, gy, gz, __int_as_float((int)f.z));
+    }
+    __syncthreads();
+    double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
+    if (t < n) {
+        for (int j = 0; j < records; ++j) {
+            const float4 ra = s.ca[j], rb = s.cb[j];
+            const int i01 = __float_as_int(ra.w), i2 = __float_as_int(rb.w);
+            if ((i01 & 0xffff) == t) { sx += (double)ra.x * (double)rb.x; sy += (double)ra.x * (double)rb.y; sz += (double)ra.x * (double)rb.z; sw += (double)ra.x; }
+            if (((i01 >> 16) & 0xffff) == t) { sx += (double)ra.y * (double)rb.x; sy += (double)ra.y * (double)rb.y; sz += (double)ra.y * (double)rb.z; sw += (double)ra.y; }
+            if (i2 == t) { sx += (double)ra.z * (double)rb.x; sy += (double)ra.z * (double)rb.y; sz += (double)ra.z * (double)rb.z; sw += (double)ra.z; }
+        }
+    }
+    return make_double4(sx, sy, sz, sw);
+}

@@ -2639,6 +2639,104 @@ def mesh_cloud_loss(verts, faces, cloud, valid=None, trim=0.03, margin=0.002, re
     return out if return_fields else out[0]
 
 
+def _one_hand_cloud_args(name, verts, faces, cloud, valid, anchor, anchor_weight, trim):
+    """The checks `mano_cloud_targets` and `mano_fit_cloud` share, on ONE hand per row: verts [B, n, 3] (None: n = 778, `mano_fit_cloud` makes
+    them), faces [Fc, 3], cloud [B, P, 3], valid [B] or None, anchor [B, n, 3] or None -> (verts, faces, cloud, valid, anchor as detached
+    contiguous f32 / int64 tensors, B, n, Fc, P, anchor_weight, trim)."""
+    f, c = faces.detach().long().contiguous(), cloud.detach().float().contiguous()
+    v = verts.detach().float().contiguous() if verts is not None else None
+    if f.dim() != 2 or f.shape[1] != 3 or c.dim() != 3 or c.shape[2] != 3 or (v is not None and (v.dim() != 3 or v.shape[2] != 3 or v.shape[0] != c.shape[0])):
+        raise ValueError("pdfnet_amd: %s wants verts [B, n, 3], faces [Fc, 3] and cloud [B, P, 3], got %s, %s and %s" % (
+            name, None if v is None else tuple(v.shape), tuple(f.shape), tuple(c.shape)))
+    B, P, Fc, n = c.shape[0], c.shape[1], f.shape[0], 778 if v is None else v.shape[1]
+    if not (1 <= n <= HAND_MAX_VERTS and 1 <= Fc <= HAND_MAX_FACES and 1 <= P <= HAND_MAX_POINTS):
+        raise ValueError("pdfnet_amd: %s takes 1 to %d vertices, 1 to %d faces and 1 to %d points per hand, got %d, %d and %d" % (
+            name, HAND_MAX_VERTS, HAND_MAX_FACES, HAND_MAX_POINTS, n, Fc, P))
+    opt = []
+    for what, x, shape in (('valid', valid, (B,)), ('anchor', anchor, (B, n, 3))):
+        if x is not None:
+            x = x.detach().float().contiguous()
+            if tuple(x.shape) != shape:
+                raise ValueError("pdfnet_amd: %s wants %s %s, got %s" % (name, what, shape, tuple(x.shape)))
+        opt.append(x)
+    trim, anchor_weight = float(trim), float(anchor_weight)
+    if not 0.0 < trim < float('inf'):
+        raise ValueError("pdfnet_amd: %s takes a finite trim > 0, got %r" % (name, trim))
+    if not 0.0 <= anchor_weight < float('inf'):
+        raise ValueError("pdfnet_amd: %s takes a finite anchor_weight >= 0, got %r" % (name, anchor_weight))
+    return v, f, c, opt[0], opt[1], B, n, Fc, P, anchor_weight, trim
+
+
+def mano_cloud_targets(verts, faces, cloud, valid=None, trim=0.03, anchor=None, anchor_weight=0.0, return_fields=False):
+    """ONE hand per row: verts [B, n, 3] camera-space metres, faces [Fc, 3] int64 (that hand's, oriented outwards), cloud [B, P, 3] its sensor
+    points (a point with Z <= 0 is ignored), valid [B] or None, anchor [B, n, 3] or None -> (target [B, n, 3], weight [B, n], rms [B], inliers
+    int32 [B]): the per-vertex targets and weights whose energy sum_v weight_v |M_v - target_v|^2 majorises, for any mesh M and with equality at
+    M = verts, the point-to-surface energy of the association of `mesh_icp(iters=0)` (made by the same device code) plus anchor_weight
+    |M_v - anchor_v|^2 -- what `mano_fit(target, weight=weight)` minimises.  weight = W_v + anchor_weight with W_v the barycentric weight the
+    inliers put on the vertex; target = (W_v v + S_v + anchor_weight a_v) / weight, S_v the weighted sum of the inliers' residuals p - q; a
+    vertex with weight 0 has target = v.  rms / inliers as `mesh_icp`'s.  A row with valid = 0 or without a usable point gets the anchor alone.
+    return_fields: also (tri int32 [B, P], bary [B, P, 3], closest [B, P, 3]) as `cloud_mesh_loss`'s.
+    The contract is `pdf_mano_cloud_targets`'s in pdfnet_hip.h.  n, P <= 1024, Fc <= 2048.  One launch; no gradient; deterministic."""
+    hip.require_gpu(verts, faces, cloud, valid, anchor)
+    v, f, c, va, an, B, n, Fc, P, alpha, trim = _one_hand_cloud_args('mano_cloud_targets', verts, faces, cloud, valid, anchor, anchor_weight, trim)
+    dev = v.device
+    target, weight = torch.empty_like(v), torch.empty((B, n), dtype=torch.float32, device=dev)
+    rms, inliers = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+    tri = torch.empty((B, P), dtype=torch.int32, device=dev) if return_fields else None
+    bary, closest = (torch.empty_like(c), torch.empty_like(c)) if return_fields else (None, None)
+    _L().pdf_mano_cloud_targets(ptr(v), ptr(f), ptr(c), ptr(va), ptr(an), alpha, B, n, Fc, P, trim, ptr(target), ptr(weight), ptr(rms), ptr(inliers),
+                                ptr(tri), ptr(closest), ptr(bary), stream())
+    return (target, weight, rms, inliers, tri, bary, closest) if return_fields else (target, weight, rms, inliers)
+
+
+ManoFitCloud = collections.namedtuple('ManoFitCloud', 'root pose shape trans params verts joints rms inliers cost info')
+MANO_FIT_CLOUD_MAX_OUTER = 64
+
+
+def mano_fit_cloud(consts, cloud, faces, init, side='left', valid=None, anchor=None, anchor_weight=0.0, outer=8, inner=3, trim=0.03,
+                   prior_pose=0.0, prior_shape=0.0):
+    """ONE hand per row: cloud [B, P, 3] that hand's sensor points, faces [Fc, 3] the MANO mesh's faces (oriented outwards), init [B, 61] =
+    [root 3 | pose 45 | shape 10 | trans 3] -> the MANO hand that agrees with the cloud: `outer` times, `mano_cloud_targets` at the current mesh
+    (trim, anchor [B, 778, 3] or None, anchor_weight) and then `inner` Levenberg-Marquardt trial steps of `mano_fit` against those targets and
+    weights from the current parameters (the damping restarts every time); valid [B] or None: a row with valid == 0 stays at init.
+    -> ManoFitCloud(root, pose, shape, trans: views of params [B, 61]; verts [B, 778, 3], joints [B, 21, 3]; rms [outer + 1, B] and inliers int32
+    [outer + 1, B]: the association at every mesh on the way, [0] at M(init), [outer] at the result; cost [outer, B, 2] = the surrogate energy
+    before and after each outer iteration's steps, info int32 [outer, B, 2] = its accepted and rejected steps).
+    The contract is `pdf_mano_fit_cloud`'s in pdfnet_hip.h.  2 outer + 2 launches on the current stream, no host sync; no gradient; deterministic."""
+    ks = ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'weights')
+    hip.require_gpu(cloud, faces, init, valid, anchor, *(consts[k] for k in ks))
+    if side not in ('left', 'right'):
+        raise ValueError("pdfnet_amd: mano_fit_cloud takes side 'left' or 'right', got %r" % (side,))
+    if init is None:
+        raise ValueError("pdfnet_amd: mano_fit_cloud needs init [B, 61] (e.g. `mano_fit`'s parameters of the predicted mesh)")
+    _, f, c, va, an, B, _, Fc, P, alpha, trim = _one_hand_cloud_args('mano_fit_cloud', None, faces, cloud, valid, anchor, anchor_weight, trim)
+    p0 = init.detach().float().contiguous()
+    if tuple(p0.shape) != (B, 61):
+        raise ValueError("pdfnet_amd: mano_fit_cloud wants init %s, got %s" % ((B, 61), tuple(p0.shape)))
+    for k, shape in zip(ks, ((778, 3), (778, 3, 10), (778, 3, 135), (16, 778), (778, 16))):
+        x = consts[k]
+        if tuple(x.shape) != shape or x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("pdfnet_amd: mano_fit_cloud wants consts[%r] contiguous float32 %s, got %s %s" % (k, shape, x.dtype, tuple(x.shape)))
+    outer, inner, prior_pose, prior_shape = int(outer), int(inner), float(prior_pose), float(prior_shape)
+    if not (0 <= outer <= MANO_FIT_CLOUD_MAX_OUTER and 1 <= inner <= MANO_FIT_MAX_ITERS):
+        raise ValueError("pdfnet_amd: mano_fit_cloud takes 0 to %d outer and 1 to %d inner iterations, got %r and %r" % (
+            MANO_FIT_CLOUD_MAX_OUTER, MANO_FIT_MAX_ITERS, outer, inner))
+    if not (0.0 <= prior_pose < float('inf') and 0.0 <= prior_shape < float('inf')):
+        raise ValueError("pdfnet_amd: mano_fit_cloud takes finite priors >= 0, got %r and %r" % (prior_pose, prior_shape))
+    dev = c.device
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+    params, verts, joints = f32(B, 61), f32(B, 778, 3), f32(B, 21, 3)
+    rms, inliers, cost, info = f32(outer + 1, B), i32(outer + 1, B), f32(outer, B, 2), i32(outer, B, 2)
+    L = _L()
+    ws = _ws(L.pdf_mano_fit_cloud_workspace_floats(B, outer), dev) if B > 0 else None
+    L.pdf_mano_fit_cloud(ptr(c), ptr(f), ptr(va), ptr(p0), ptr(an), alpha, trim, outer, inner, prior_pose, prior_shape,
+                         ptr(consts['v_template']), ptr(consts['shapedirs']), ptr(consts['posedirs']), ptr(consts['J_regressor']),
+                         ptr(consts['weights']), B, Fc, P, int(side == 'left'), ptr(params), ptr(verts), ptr(joints), ptr(rms), ptr(inliers),
+                         ptr(cost) if outer else None, ptr(info) if outer else None, ptr(ws), stream())
+    return ManoFitCloud(params[:, :3], params[:, 3:48], params[:, 48:58], params[:, 58:], params, verts, joints, rms, inliers, cost, info)
+
+
 class _PenetrationLoss(torch.autograd.Function):
     """loss [..., 2] of `penetration_loss`; the kernel writes both gradients (with respect to the hand's own vertices and to the other hand's) in
     the forward launch when verts needs them."""

@@ -625,7 +625,7 @@ class Trainer:
 
 
     def evaluation(self, loader, device=None, score_path=None, json_path=None, aligned=False, interaction=False, rendered=False, refined=False,
-                   two_sided=False, mano_fit=False):
+                   two_sided=False, mano_fit=False, cloud_fit=False):
         """Counterpart of `BaseTrainer.evaluation` (lib/trains/base_trainer.py:207-429, H2O branch): the test-mode pass
         (centres from the predicted heat-map, root from the predicted depth) and the mean Euclidean errors per hand --
         absolute and root-relative joints / vertices in mm, 2-D landmarks in pixels.  The reference evaluates on rank 0
@@ -660,7 +660,11 @@ class Trainer:
         mano_fit:   False, or `load_mano_constants`' lbs_consts ({'left' / 'right': the constants `F.mano_lbs` takes}): also how far the meshes
                     are from the space of MANO hands -- every valid predicted and ground-truth absolute mesh is fitted by `F.mano_fit`
                     (MANO_FIT_ITERS Levenberg-Marquardt steps, one launch per hand and mesh set): the keys of `finish_mano_fit`.  One more
-                    accumulator in the same buffer.  The other keys do not change."""
+                    accumulator in the same buffer.  The other keys do not change.
+        cloud_fit:  False, or lbs_consts as `mano_fit` takes them: also the articulated hand that agrees with the sensor -- per valid hand,
+                    `F.mano_fit` of the predicted absolute mesh gives the start, and `F.mano_fit_cloud` (CLOUD_FIT_OUTER x CLOUD_FIT_INNER steps,
+                    REFINE_TRIM, the predicted mesh as anchor with CLOUD_FIT_ANCHOR) fits it to that hand's points batch['cloud']: the keys of
+                    `finish_cloud_fit`.  One more accumulator in the same buffer; needs `faces_pair`.  The other keys do not change."""
         if refined not in (False, True, 'translation', 'rigid'):
             raise ValueError("Trainer.evaluation: refined is False, True, 'translation' or 'rigid', got %r" % (refined,))
         mwl = self.model_with_loss
@@ -684,6 +688,8 @@ class Trainer:
                 acc6 = torch.zeros(TWO_SIDED_SUMS, dtype=torch.float64, device=dev)    # see two_sided_sums
             if mano_fit:
                 acc7 = torch.zeros(MANO_FIT_SUMS, dtype=torch.float64, device=dev)     # see mano_fit_sums
+            if cloud_fit:
+                acc8 = torch.zeros(CLOUD_FIT_SUMS, dtype=torch.float64, device=dev)    # see cloud_fit_sums
             poses = []
             with torch.no_grad():
                 for batch in loader:
@@ -704,6 +710,8 @@ class Trainer:
                         acc6 += two_sided_sums(tup, batch, mwl.loss.faces_pair)
                     if mano_fit:
                         acc7 += mano_fit_sums(tup, batch, mano_fit)
+                    if cloud_fit:
+                        acc8 += cloud_fit_sums(tup, batch, mwl.loss.faces_pair, cloud_fit)
                     if json_path is not None:
                         if 'id' not in batch or 'frame_num' not in batch:
                             raise KeyError("Trainer.evaluation: hand_poses.json needs batch['id'] and batch['frame_num'] (interhand.py H2O entries)")
@@ -713,6 +721,9 @@ class Trainer:
                         poses.append(torch.cat((key, jp.reshape(jp.shape[0], -1).double()), 1))          # [B, 2 + 126]
             if aligned:                                            # one buffer for the reduction and the copy (the counts are exact in float64)
                 acc = torch.cat((acc, acc2, pck.reshape(-1).double()))
+            if cloud_fit:                                          # before the MANO-fit block
+                ct = acc.numel()
+                acc = torch.cat((acc, acc8))
             if mano_fit:                                           # before the two-sided block
                 mt = acc.numel()
                 acc = torch.cat((acc, acc7))
@@ -743,6 +754,8 @@ class Trainer:
                 out.update(finish_two_sided(acc[tt:tt + TWO_SIDED_SUMS]))
             if mano_fit:
                 out.update(finish_mano_fit(acc[mt:mt + MANO_FIT_SUMS]))
+            if cloud_fit:
+                out.update(finish_cloud_fit(acc[ct:ct + CLOUD_FIT_SUMS]))
             if json_path is not None:
                 rows = torch.cat(poses) if poses else torch.zeros((0, 128), dtype=torch.float64, device=dev)
                 if self.world > 1:                                 # ragged gather: pad every rank's block to the longest
@@ -1156,6 +1169,77 @@ def write_mano_fit_scores(path, ev):
     with open(path, 'a') as fo:
         fo.write('eval mano-fit \n')
         for k in MANO_FIT_KEYS:
+            if k in ev:
+                fo.write('%s: %.2f\n' % (k, ev[k]))
+
+
+CLOUD_FIT_KEYS = ('cloud_fit_mpjpe_mm', 'cloud_fit_mpvpe_mm', 'cloud_fit_res0_mm', 'cloud_fit_res_mm', 'cloud_fit_inlier_share0',
+                  'cloud_fit_inlier_share', 'cloud_fit_accepted', 'cloud_fit_samples')
+CLOUD_FIT_SUMS = 21
+CLOUD_FIT_OUTER = 8                          # associations of the evaluation's fit to the cloud
+CLOUD_FIT_INNER = 3                          # Levenberg-Marquardt trial steps per association
+CLOUD_FIT_ANCHOR = 0.1                       # weight of the predicted mesh per vertex; a vertex the sensor sees collects about P / n from its points
+
+
+def cloud_fit_sums(tup, batch, faces, lbs_consts):
+    """test-mode 9-tuple, the batch (`cloud` [B, 2, P, 3] camera-space metres, `valid` [B, 2]), the faces [2, Fc, 3] and `load_mano_constants`'
+    lbs_consts -> float64 [21] on the device.  Per hand, `mano_fit_pair` of the predicted absolute mesh (MANO_FIT_ITERS steps) gives the start
+    and `mano_fit_cloud_pair` fits it to the cloud, the predicted mesh as anchor.  [0] the number of samples; then, per quantity, the pair (left,
+    right) of sums over the samples with that hand valid (valid == 1): [1:3] the fitted joints' and [3:5] the fitted vertices' mean distance to
+    the ground truth, [5:7] / [7:9] the root mean square inlier distance of the cloud to the start / to the fitted mesh, [9:11] / [11:13] the
+    inliers / usable points at the start / at the end, [13:15] the accepted steps, [15:17] the number of such samples, and those of them with
+    an inlier [17:19] at the start, [19:21] at the end (what the residuals' means are over)."""
+    from ..utils import mano_fit_pair, mano_fit_cloud_pair
+    vp, _, vg, jg = tup[:4]
+    if 'cloud' not in batch:
+        raise KeyError("Trainer.evaluation: cloud_fit needs batch['cloud'], the hands' sensor points [B, 2, P, 3] in camera-space metres "
+                       "(F.depth2pcl, interhand.py H2O entries)")
+    cloud, valid = batch['cloud'], batch['valid']
+    start = mano_fit_pair(lbs_consts, vp, valid, iters=MANO_FIT_ITERS)
+    init = torch.stack([torch.cat((f.root, f.pose, f.shape, f.trans), 1) for f in start], 1)     # [B, 2, 61]
+    fit = mano_fit_cloud_pair(lbs_consts, faces, cloud, init, valid=valid, anchor=vp.float(), anchor_weight=CLOUD_FIT_ANCHOR, outer=CLOUD_FIT_OUTER,
+                              inner=CLOUD_FIT_INNER, trim=REFINE_TRIM)
+    fv, fj = (torch.stack((a, b), 1) for a, b in ((fit[0].verts, fit[1].verts), (fit[0].joints, fit[1].joints)))
+    rms, inl, acc = (torch.stack((getattr(fit[0], k), getattr(fit[1], k)), -1) for k in ('rms', 'inliers', 'info'))      # [outer + 1, B, 2] x 2, [outer, B, 2, 2]
+    has = valid == 1                                                                             # [B, 2]
+    live = (cloud[..., 2] > 0).sum(-1).double().clamp(min=1)
+    terms = torch.stack((F.point_dist_sum(fj, jg).double() / jg.shape[-2], F.point_dist_sum(fv, vg).double() / vg.shape[-2], rms[0].double(),
+                         rms[-1].double(), inl[0].double() / live, inl[-1].double() / live, acc[:, :, 0, :].double().sum(0),
+                         torch.ones(has.shape, dtype=torch.float64, device=vp.device), (inl[0] > 0).double(), (inl[-1] > 0).double()))      # [10, B, 2]
+    n = torch.full((1,), float(vp.shape[0]), dtype=torch.float64, device=vp.device)
+    return torch.cat((n, torch.where(has, terms, torch.zeros_like(terms)).sum(1).reshape(-1)))
+
+
+def finish_cloud_fit(acc):
+    """The accumulator of `cloud_fit_sums` -> 'cloud_fit_mpjpe_mm' / 'cloud_fit_mpvpe_mm' (absolute errors of the cloud-fitted MANO hand, mean of
+    the two hands' means over the samples with that hand valid, or of the one there is), 'cloud_fit_res0_mm' / 'cloud_fit_res_mm' (root mean
+    square inlier distance of the cloud to the start mesh / to the fitted mesh, mean over the hands with an inlier), 'cloud_fit_inlier_share0' /
+    'cloud_fit_inlier_share' (inliers / usable points before / after, mean over the valid hands), 'cloud_fit_accepted' (accepted
+    Levenberg-Marquardt steps of the CLOUD_FIT_OUTER x CLOUD_FIT_INNER, mean over the valid hands), 'cloud_fit_samples'.  A mean over nothing
+    is 0; without a sample only 'cloud_fit_samples'."""
+    a = [float(x) for x in acc]
+    out = {'cloud_fit_samples': int(round(a[0]))}
+    if out['cloud_fit_samples'] == 0:
+        return out
+    mean = lambda total, count: total / count if round(count) > 0 else 0.0
+    res = {}
+    for i, key in ((1, 'cloud_fit_mpjpe_mm'), (3, 'cloud_fit_mpvpe_mm')):
+        there = [a[i + h] / a[15 + h] * 1000 for h in range(2) if round(a[15 + h]) > 0]
+        res[key] = sum(there) / len(there) if there else 0.0
+    res['cloud_fit_res0_mm'] = mean(a[5] + a[6], a[17] + a[18]) * 1000
+    res['cloud_fit_res_mm'] = mean(a[7] + a[8], a[19] + a[20]) * 1000
+    res['cloud_fit_inlier_share0'] = mean(a[9] + a[10], a[15] + a[16])
+    res['cloud_fit_inlier_share'] = mean(a[11] + a[12], a[15] + a[16])
+    res['cloud_fit_accepted'] = mean(a[13] + a[14], a[15] + a[16])
+    res.update(out)
+    return {k: res[k] for k in CLOUD_FIT_KEYS}
+
+
+def write_cloud_fit_scores(path, ev):
+    """Append the figures of `evaluation(cloud_fit=...)` that are there as a block of their own (`key: %.2f`, like `write_mano_fit_scores`)."""
+    with open(path, 'a') as fo:
+        fo.write('eval cloud-fit \n')
+        for k in CLOUD_FIT_KEYS:
             if k in ev:
                 fo.write('%s: %.2f\n' % (k, ev[k]))
 

@@ -99,6 +99,25 @@ def mano_fit_pair(lbs_consts, verts, valid=None, **kw):
     return tuple(out)
 
 
+def mano_fit_cloud_pair(lbs_consts, faces_pair, cloud, init_pair, valid=None, anchor=None, **kw):
+    """faces_pair [2, Fc, 3] (left, right: the loss module's), cloud [B, 2, P, 3] each hand's sensor points, init_pair [B, 2, 61], valid [B, 2]
+    or None, anchor [B, 2, 778, 3] or None -> (left, right): `F.mano_fit_cloud` of each hand with its own constants and faces; **kw goes to
+    `F.mano_fit_cloud` (anchor_weight, outer, inner, trim, priors)."""
+    if cloud.dim() != 4 or cloud.shape[1] != 2 or cloud.shape[3] != 3:
+        raise ValueError("pdfnet_amd: mano_fit_cloud_pair wants cloud [B, 2, P, 3], got %s" % (tuple(cloud.shape),))
+    B = cloud.shape[0]
+    if faces_pair.dim() != 3 or faces_pair.shape[0] != 2 or faces_pair.shape[2] != 3:
+        raise ValueError("pdfnet_amd: mano_fit_cloud_pair wants faces_pair [2, Fc, 3], got %s" % (tuple(faces_pair.shape),))
+    for name, x, shape in (('init_pair', init_pair, (B, 2, 61)), ('valid', valid, (B, 2)), ('anchor', anchor, (B, 2, 778, 3))):
+        if (x is None and name == 'init_pair') or (x is not None and tuple(x.shape) != shape):
+            raise ValueError("pdfnet_amd: mano_fit_cloud_pair wants %s %s, got %s" % (name, shape, None if x is None else tuple(x.shape)))
+    out = []
+    for h, side in enumerate(('left', 'right')):
+        out.append(F.mano_fit_cloud(lbs_consts[side], cloud[:, h], faces_pair[h], init_pair[:, h], side=side,
+                                    valid=None if valid is None else valid[:, h], anchor=None if anchor is None else anchor[:, h], **kw))
+    return tuple(out)
+
+
 def load_mano_constants(npz_path, device=None):
     """`mano_constants.npz` (written at the user's site by tools/convert_mano.py from MANO_LEFT.pkl / MANO_RIGHT.pkl) ->
     (loss_consts, lbs_consts): what the reference builds in `ManoLayer.__init__` (lib/models/networks/manolayer.py:100-160),
